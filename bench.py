@@ -11,17 +11,19 @@ step ends with the text of the six output files in host memory (what est-fact wr
 raw-multifasta-out.txt etc.) plus the packed factorization records; for N > 1 the packed records are
 gathered to rank 0 over RCCL inside the step.
 Not in the step: reading genomic.txt/ests.txt, strand/polyA preparation, index construction (done
-once, reported as load_s / index_s), writing the files.  What a user who brings a NEW batch gets is in
-the same line: `fresh_batch` (two distinct batches alternate; reading and preparing the input, building the index,
+once, reported as load_s / index_s), writing the files.
+
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs DIR) and prints
+its line.  Everything else is measured and checked with --full only, in the same line: what a user who brings a
+NEW batch gets, `fresh_batch` (two distinct batches alternate; reading and preparing the input, building the index,
 uploading the patterns and the step are all inside the timed region, every output md5-checked against the
-reference's) and `oneshot` (one est-fact process, start to files on disk).  `other_workloads`: short legs of
-the other single-GPU shares of BASELINE.json (C5 share, C2), md5-checked, each with its own roofline.
+reference's) and `oneshot` (one est-fact process, start to files on disk); `other_workloads`: short legs of
+the other single-GPU shares of BASELINE.json (C5 share, C2), md5-checked, each with its own roofline; the md5 of
+the timed step's output against the reference's (`timed_output`), the records rank 0 gathered (`gathered`); and
+a bounded sample of the same workload run through the reference CPU est-fact (oracle/_ref/est-fact-core, the
+cpu_baseline) and through this code, whose two raw-multifasta-out.txt must be byte-identical.
 
-The output of the timed steps is checked: a bounded sample of the same workload is run through the
-reference CPU est-fact (oracle/_ref/est-fact-core, the cpu_baseline) and through this code, and the
-two raw-multifasta-out.txt must be byte-identical.
-
-Contract: python bench.py --gpus N --steps K --warmup W ; one JSON line on rank 0.
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] ; one JSON line on rank 0.
 """
 import argparse
 import hashlib
@@ -45,7 +47,13 @@ CPU_SAMPLE_OF = {"C2": 1_000, "C3": 3_000, "C4": 3_000, "C5": 6_000}
 CPU_SAMPLE = CPU_SAMPLE_OF["C3"]
 
 
-from pintron_amd.estfact import RECORDS, Session, gather_tensor, load_host_lib  # noqa: E402
+from pintron_amd.estfact import (OUTPUT_FILES, RECORDS, Session, gather_tensor, load_host_lib,  # noqa: E402
+                                 parse_factorization_records)
+# --dump-outputs: bytes per array (records in float64, texts in float32): 36 + 5 x 4 MiB, under 64 MB in all
+DUMP_RECORD_BYTES = {"records_ests": 4 << 20, "records_factorizations": 8 << 20, "records_exons": 24 << 20}
+DUMP_TEXT_BYTES = 4 << 20
+# processed-megs-info.txt is left out: it holds per-EST timings, as the reference's does
+DUMP_TEXTS = [f for f in OUTPUT_FILES if f != "processed-megs-info.txt"]
 
 
 def launch_ranks(args):
@@ -215,6 +223,40 @@ def gold_md5(name, n, seed):
     return json.load(open(gold_path)).get("%s:%d:seed%d" % (name, n, seed))
 
 
+def sample_rows(a, max_bytes, seed):
+    """`a` itself, or a fixed seeded sample of its rows (in their order) when it is larger than max_bytes"""
+    import numpy as np
+    row = a.itemsize * max(1, int(np.prod(a.shape[1:])))
+    if a.nbytes <= max_bytes:
+        return a
+    idx = np.unique(np.random.default_rng(seed).integers(0, len(a), max_bytes // row))
+    return a[idx]
+
+
+def dump_outputs(directory, records, texts):
+    """What the last timed step handed its caller, as DIR/<name>.npy, for comparing two builds output by output:
+    the packed factorization records (`records`: per aligned EST [est index, factorizations], per factorization
+    [polya, polyad, exons], per exon [est start, est end, genomic start, genomic end]; float64) and the bytes of
+    the output texts (`texts`: DUMP_TEXTS -> bytes; float32, their lengths in text_lengths.npy)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    groups = parse_factorization_records(records)
+    arrays = {
+        "records_ests": np.array([(e, len(f)) for e, f in groups], dtype=np.float64).reshape(-1, 2),
+        "records_factorizations": np.array([(pa, pd, len(ex)) for _, f in groups for pa, pd, ex in f],
+                                           dtype=np.float64).reshape(-1, 3),
+        "records_exons": np.array([x for _, f in groups for _, _, ex in f for x in ex], dtype=np.float64).reshape(-1, 4)}
+    for k, (name, a) in enumerate(arrays.items()):
+        np.save(os.path.join(directory, name + ".npy"), sample_rows(a, DUMP_RECORD_BYTES[name], 11 + k))
+    lengths = []
+    for k, name in enumerate(DUMP_TEXTS):
+        b = np.frombuffer(texts[name], dtype=np.uint8)
+        lengths.append(len(b))
+        np.save(os.path.join(directory, name.replace(".txt", "").replace("-", "_") + ".npy"),
+                sample_rows(b, DUMP_TEXT_BYTES // 4, 101 + k).astype(np.float32))
+    np.save(os.path.join(directory, "text_lengths.npy"), np.array(lengths, dtype=np.float64))
+
+
 def other_workload_leg(L, synth, wl, steps=5, warmup=2):
     """A short leg of another single-GPU share of BASELINE.json (its own session, closed afterwards): the same
     measurement as the headline -- steps timed between synchronisations, output md5 against the reference's,
@@ -308,14 +350,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--ests", type=int, default=None, help="ESTs per GPU per step (default: the workload's per-GPU share, PER_GPU)")
     ap.add_argument("--genes", type=int, default=None, help="C4 only: number of genes (default 8 = BASELINE.json configs[3]; 1 = one GPU's share)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / parity leg")
-    ap.add_argument("--no-oneshot", action="store_true", help="skip the one-process start-to-files measurement")
-    ap.add_argument("--no-extra", action="store_true", help="skip the fresh-batch leg and the other workloads' legs (N = 1, default workload only)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the checks against the reference's output, the one-process and fresh-batch "
+                         "legs, the other workloads' legs and the CPU baseline (off: set up, warm up, time, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64 / float32, < 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline / parity leg")
+    ap.add_argument("--no-oneshot", action="store_true", help="--full without the one-process start-to-files measurement")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the fresh-batch leg and the other workloads' legs (N = 1, default workload only)")
     ap.add_argument("--workload", choices=("C2", "C3", "C4", "C5"), default="C3",
                     help="C3 (default, the metric's configuration): one 200 kb gene x --ests per GPU; "
                          "C4: 8 genes x 200 kb, --ests ESTs each (62 500 = BASELINE.json configs[3]), gene g on rank g mod N; "
                          "C2: 50 kb x 1 000 ESTs; C5: 1 Mb x 250 000 reads of 150 bp per GPU (an eighth of configs[4])")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.ests is None:
         args.ests = PER_GPU[args.workload]
 
@@ -409,6 +458,12 @@ def main():
         tn = torch.tensor([n_est, n_aligned], dtype=torch.int64, device=xdev)
         dist.all_reduce(tn)
         total_est, total_aligned = int(tn[0].item()), int(tn[1].item())
+    if rank == 0 and args.dump_outputs:
+        # the sharded path hands rank 0 the records of every rank; the texts are those of rank 0's own genes
+        records = b"".join(bytes(p.cpu().numpy().tobytes()) for p in gathered["parts"]) if world > 1 else \
+            b"".join(sess.output(RECORDS) for sess in sessions)
+        dump_outputs(args.dump_outputs, records,
+                     {f: b"".join(sess.output(OUTPUT_FILES.index(f)) for sess in sessions) for f in DUMP_TEXTS})
     if rank == 0:
         st = stats[-1][-1]
         kernels = kernels_of(stats, args.steps)
@@ -435,7 +490,6 @@ def main():
                        "dp_batches_per_step": int(sum(x.dp_batches for x in stats[-1])),
                        "parallelism": "est-shard x%d" % world},
             "dp_mcells_per_s": sum(k["cells"] for k in kernels.values()) * world / step_s / 1e6,
-            "timed_output_md5": hashlib.md5(b"".join(sess.records() for sess in sessions)).hexdigest(),
             "phases_s": {"load_once": st.load_s, "index_once": st.index_s, "prefetch_pairings": st.prefetch_s,
                          "workers_wall": st.workers_s, "host_cpu_per_thread": st.host_s / st.threads,
                          "dp_batches_per_thread": st.dp_s / st.threads},
@@ -447,8 +501,10 @@ def main():
         }
         # the text the LAST TIMED step left on rank 0 against the reference's checksum for the very same
         # batch (tools/make_bench_md5.py ran the reference object code on it in the build container)
+        if args.full:
+            out["timed_output_md5"] = hashlib.md5(b"".join(sess.records() for sess in sessions)).hexdigest()
         gold_path = os.path.join(ROOT, "tests", "golden", "bench_md5.json")
-        if os.path.exists(gold_path):
+        if args.full and os.path.exists(gold_path):
             # every gene of this rank whose batch has a committed checksum (C4: gene 0 = one GPU's share)
             table = json.load(open(gold_path))
             checked = []
@@ -464,7 +520,7 @@ def main():
                                      % (checked[-1]["batch"], md5, gold["raw-multifasta-out.txt"]))
             if checked:
                 out["timed_output"] = dict(checked[0], ests=n_est, batches_checked=len(checked))
-        if world == 1 and wl != "C4" and not args.no_oneshot:
+        if args.full and world == 1 and wl != "C4" and not args.no_oneshot:
             # the way the pipeline driver uses est-fact (dist-scripts/pintron.py:878-884): one process per
             # gene, process start -> the six files on disk.  Outside the timed steps; the resident
             # sessions above keep their HBM.
@@ -477,7 +533,7 @@ def main():
                 out["oneshot"] = {"seconds": t_one, "ESTs_per_s": n_est / t_one,
                                   "what": "est-fact process start -> six files on disk, same %d-EST batch" % n_est,
                                   "md5_equals_timed_step": hashlib.md5(raw).hexdigest() == out["timed_output_md5"]}
-        if world > 1 and "parts" in gathered:
+        if args.full and world > 1 and "parts" in gathered:
             # what rank 0 holds after the last step's gather: the record groups of every rank (one per aligned EST)
             from pintron_amd.estfact import parse_factorization_records
             sizes = [int(p.numel()) for p in gathered["parts"]]
@@ -487,14 +543,14 @@ def main():
                 raise SystemExit("bench: rank 0 received %d record groups for %d aligned ESTs" % (groups, total_aligned))
         if kernels:
             out["roofline"], out["kernels"] = roofline_of(kernels, n_est, wl)
-        if world == 1 and wl == "C3" and args.ests == PER_GPU["C3"] and not args.no_extra:
+        if args.full and world == 1 and wl == "C3" and args.ests == PER_GPU["C3"] and not args.no_extra:
             # the resident sessions above are done: their HBM and threads go before the other legs start
             for sess in sessions:
                 sess.close()
             sessions = []
             out["fresh_batch"] = fresh_batch_leg(L, synth, "C3", args.ests, [synth.CONFIGS["C3"]["seed"], 1003])
             out["other_workloads"] = [other_workload_leg(L, synth, w2) for w2 in ("C5", "C2")]
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             # bounded sample of the same workload: reference CPU est-fact vs this code, byte for byte
             cpu_n = min(CPU_SAMPLE_OF[wl], n_est)
             sample = synth.make(wl, n_est=cpu_n, seed=genes[0][1])

@@ -49,7 +49,7 @@ def run_bench(world, genes, tmp_path, port):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--workload", "C4", "--genes", str(genes), "--ests", "12", "--steps", "1", "--warmup", "0",
-           "--no-cpu", "--no-oneshot"]
+           "--no-cpu", "--no-oneshot", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

@@ -255,7 +255,7 @@ def test_bench_flow_with_two_ranks_on_one_gpu(exe, tmp_path):
     env = dict(os.environ, PINTRON_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "1", "--ests", "6000", "--no-cpu"]
+           "--gpus", "2", "--steps", "1", "--warmup", "1", "--ests", "6000", "--no-cpu", "--full"]
     out = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -314,7 +314,7 @@ def test_c4_two_gene_sample_vs_compiled_reference(exe, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "C4", "--ests", "1500",
-                          "--steps", "1", "--warmup", "0"], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
+                          "--steps", "1", "--warmup", "0", "--full"], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["scaling"] == "strong" and d["config"]["ests_per_gpu"] == 8 * 1500 and d["n_gpus"] == 1
