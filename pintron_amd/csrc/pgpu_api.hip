@@ -33,18 +33,12 @@ struct pgpu_ctx {
   char err[512] = {0};
   BufPool pools[2];          // 0: DP plans, 1: pairing plans
   bool timing = false;       // HIP events around every kernel group (bench / profiling)
-  // the kernel groups of one DP plan are independent of each other: they are spread over a few
-  // auxiliary streams so that a batch costs max(group) instead of sum(group) in latency
-  static constexpr int NAUX = 8;
+  // the kernel groups of one DP plan are independent of each other: the ones outside the batch launch are
+  // spread over four auxiliary streams so that a batch costs max(group) instead of sum(group) in latency
+  static constexpr int NAUX = 4;
   hipStream_t aux[NAUX] = {nullptr};
   hipEvent_t ev_upload = nullptr;
   hipEvent_t ev_aux[NAUX] = {nullptr};
-  bool fanout = true;        // spread groups over the auxiliary streams (PGPU_FANOUT=0 disables)
-  int n_aux = NAUX;          // how many of them are used (PGPU_STREAMS=1..8)
-  int merged = 2;            // 2: the latency-bound part of a batch (one-job-per-workgroup sweeps + every wave-per-job
-                             //    family) in ONE launch beside the LCF launch; 1: the wave-per-job families in one
-                             //    launch, the sweeps in theirs; 0: a launch per family (PGPU_MERGED)
-  bool packed = true;        // four streams, kernel families packed by expected duration (PGPU_PACK=0: round-robin over n_aux)
   // waiting: the calling thread must not burn a host core that other EST fibres could use (the
   // default HIP wait spins).  It naps and polls the event: measured on C3, naps of 50-200 us beat
   // a blocking-sync event by 5-7 % whole-program (the interrupt path costs more host time than
@@ -52,10 +46,6 @@ struct pgpu_ctx {
   hipEvent_t ev_done = nullptr;
   hipEvent_t ev_wait = nullptr;      // pgpu_ctx_wait (pairing / MEG stages)
   long wait_poll_us = 20;
-  bool align_coop = true;    // ALIGN with 65 .. 4096 rows on four waves (PGPU_ALIGN_COOP=0: one wave, as before)
-  bool align_band = true;    // ALIGN above 64 rows: inside a band on one wave first (PGPU_ALIGN_BAND=0: always the whole matrix)
-  bool lcf_sa_n = true;      // ... also for an EST prefix with one N (PGPU_LCF_SA_N=0: those take the DP kernel, as before)
-  bool lcf_sa = true;        // longest common factors of genomic prefixes from the suffix array (PGPU_LCF_SA=0: always the DP kernel)
   int poison = -1;           // PGPU_POISON=<0..255>: fill strings + workspace of every DP plan with that byte first
   // pinned staging for the device->host result copies (pageable copies block and spin inside HIP)
   void* pin[2] = {nullptr, nullptr};
@@ -270,20 +260,12 @@ extern "C" int pgpu_init(int device, pgpu_ctx** out) {
     return PGPU_EDEVICE;
   }
   // the auxiliary streams are made when a plan first forks onto them (aux_stream): a stream costs ~5 ms and
-  // ~17 MB of host memory in the runtime, and the default one-launch batch forks only for LCF jobs with an N
+  // ~17 MB of host memory in the runtime, and the one-launch batch forks only for LCF jobs with an N
   if (hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming) != hipSuccess) { delete ctx; return PGPU_EDEVICE; }
   if (hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) { delete ctx; return PGPU_EDEVICE; }
   if (hipEventCreateWithFlags(&ctx->ev_wait, hipEventDisableTiming) != hipSuccess) { delete ctx; return PGPU_EDEVICE; }
-  { const char* f = getenv("PGPU_FANOUT"); ctx->fanout = !(f && f[0] == '0'); }
   { const char* f = getenv("PGPU_WAIT"); if (f) ctx->wait_poll_us = atol(f); }
-  { const char* f = getenv("PGPU_ALIGN_COOP"); if (f && f[0] == '0') ctx->align_coop = false; }
-  { const char* f = getenv("PGPU_LCF_SA"); if (f && f[0] == '0') ctx->lcf_sa = false; }
-  { const char* f = getenv("PGPU_LCF_SA_N"); if (f && f[0] == '0') ctx->lcf_sa_n = false; }
-  { const char* f = getenv("PGPU_ALIGN_BAND"); if (f && f[0] == '0') ctx->align_band = false; }
   { const char* f = getenv("PGPU_POISON"); if (f && f[0]) ctx->poison = atoi(f) & 255; }
-  { const char* f = getenv("PGPU_PACK"); if (f && atoi(f) == 0) ctx->packed = false; }
-  { const char* f = getenv("PGPU_MERGED"); if (f && atoi(f) >= 0 && atoi(f) <= 2) ctx->merged = atoi(f); }
-  { const char* f = getenv("PGPU_STREAMS"); const int v = f ? atoi(f) : 0; if (v >= 1 && v <= pgpu_ctx::NAUX) { ctx->n_aux = v; ctx->packed = false; } }
   base_event(device, ctx->stream);
   *out = ctx;
   return PGPU_OK;
@@ -321,9 +303,8 @@ struct Group {
   uint32_t max_chunks = 0, max_l2 = 0;
   uint32_t n_big = 0;          // leading jobs of the large row classes (ED, ALIGN, KBAND: above 16 rows per lane; GAP: above 4)
   uint32_t max_rows = 0;       // largest a_len of the group (LDS of the one-job-per-workgroup BORDERS kernel)
-  bool traceback = false;      // this group is the traceback pass of (family)
   bool launched = false;       // its events were recorded by the last launch
-  bool in_merged = false;      // its common row classes run inside the plan's merged launch; what is left here is the BIG part
+  bool in_merged = false;      // its common row classes run inside the plan's batch launch; what is left here is the BIG part
   uint64_t cells = 0, algo_bytes = 0;
   uint64_t cells_big = 0, algo_big = 0;     // share of the first n_big jobs
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -364,14 +345,12 @@ struct pgpu_dp_plan {
   uint8_t* d_base = nullptr;
   uint8_t* h_up = nullptr; uint8_t* h_down = nullptr;
   size_t up_bytes = 0, off_results = 0, down_bytes = 0;
-  // merged launch (wave_jobs_kernel): segments = the common row classes of the wave-per-job families
+  // batch launch (dp_batch_kernel): segments = the common row classes of the wave-per-job families ...
   int n_segs = 0, seg_family[MAX_WAVE_SEGS] = {0}, seg_start[MAX_WAVE_SEGS] = {0}, seg_count[MAX_WAVE_SEGS] = {0};
   LcfIndexView lcf_ix{};       // the index view the suffix-array LCF jobs search (one index per plan)
-  int merged_group = -1;       // index of the pseudo group that carries its timing and accounting
-  // ... and, with the batch kernel, the one-job-per-workgroup BORDERS / AFFIX jobs
-  bool batch = false;
+  // ... and the one-job-per-workgroup BORDERS / AFFIX / ALIGN jobs
   int bc_start = 0, bc_count = 0, ac_start = 0, ac_count = 0, lc_start = 0, lc_count = 0;   // BORDERS / AFFIX / ALIGN on several waves
-  int ab_start = 0, ab_count = 0;              // banded ALIGN jobs of the merged launch (the follow-up launch looks at them)
+  int ab_start = 0, ab_count = 0;              // banded ALIGN jobs of the batch launch (the follow-up launch looks at them)
   uint32_t bc_max_rows = 0;
   // LCF: the kernel leaves one 64-bit key per job directly in front of the results; they come back in the
   // same copy and sync turns them into results (lcf_out[k] = caller index of the job of key k)
@@ -411,7 +390,7 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
     if ((parts[q].n_jobs && !parts[q].jobs) || (parts[q].arena_len && !parts[q].arena)) return set_err(ctx, PGPU_EINVAL, "bad argument");
     n_jobs += parts[q].n_jobs; arena_len += parts[q].arena_len;
   }
-  if (n_jobs > 0x7fffffffu) return set_err(ctx, PGPU_EINVAL, "too many jobs");
+  if (n_jobs >= (size_t)1 << 30) return set_err(ctx, PGPU_EINVAL, "too many jobs");   // (the batch launch counts them in int)
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   pgpu_dp_plan* p = new (std::nothrow) pgpu_dp_plan();
   if (!p) return set_err(ctx, PGPU_ENOMEM, "out of host memory");
@@ -421,8 +400,7 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
   const uint8_t* d_gen = idx ? pgpu_index_genomic(idx) : nullptr;
   const size_t gen_len = idx ? pgpu_index_length(idx) : 0;
   p->lcf_ix = pgpu_index_lcf_view(idx);
-  const bool lcf_sa = ctx->lcf_sa && idx && p->lcf_ix.focc && p->lcf_ix.rmq;
-  const bool align_coop = ctx->align_coop;
+  const bool lcf_sa = idx && p->lcf_ix.focc && p->lcf_ix.rmq;
   p->owner = ctx;
   p->pooled = pgpu_ctx_pool_acquire(ctx, 0);
 
@@ -459,9 +437,8 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
         // exon against its stretch of the genomic sequence: the alignment hugs the diagonal.  Above 64 rows, lengths
         // within the band's half-width: inside the band on ONE wave among the wave-per-job jobs (four to a workgroup
         // instead of a workgroup each); the rare job the band cannot settle is finished by the follow-up launch
-        if (ctx->align_band && align_coop && ctx->merged >= 1 && la > 64u && la <= 4096u && (la > lb ? la - lb : lb - la) <= ALIGN_BAND_HALF)
+        if (la > 64u && la <= 4096u && (la > lb ? la - lb : lb - la) <= ALIGN_BAND_HALF)
           k.family = KF_ALIGNB;
-        k.j.tail = 0u;
         break;
       case PGPU_DP_GAP:
         if (lb > PGPU_MAX_GAP_SIDE || la > PGPU_MAX_GAP_SIDE || ((uint64_t)la + 1) * ((uint64_t)lb + 1) > PGPU_MAX_GAP_CELLS) continue;
@@ -493,10 +470,10 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
             if (b[q] == 'N' || b[q] == 'n') { ++n_wild; wild_at = q; }
             else acgt = b[q] == 'A' || b[q] == 'C' || b[q] == 'G' || b[q] == 'T';
           }
-          if (acgt && n_wild <= (ctx->lcf_sa_n ? 1u : 0u)) { k.family = KF_LCFSA; k.j.p0 = n_wild ? wild_at + 1u : 0u; }
+          if (acgt && n_wild <= 1u) { k.family = KF_LCFSA; k.j.p0 = n_wild ? wild_at + 1u : 0u; }
         }
         // two short strings: one wave (a lane per diagonal) instead of a workgroup and an atomic per job
-        if (k.family == KF_LCF && ctx->lcf_sa && (uint64_t)la * lb <= 16384u && la + lb <= 4096u) k.family = KF_LCFW;
+        if (k.family == KF_LCF && (uint64_t)la * lb <= 16384u && la + lb <= 4096u) k.family = KF_LCFW;
         break;
       }
       case PGPU_DP_BORDERS:
@@ -554,11 +531,9 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
         ws += (size_t)((la + 4095u) / 4096u) * ((size_t)lb + 64) * 64 * align_entry_bytes(k.R);
         k.j.str_off = strs; strs += 2 * ((size_t)la + lb + 1);
       }
-    } else if ((k.family == KF_ALIGN || k.family == KF_ALIGNB) && k.R >= 2 && ctx->align_coop) {   // four waves: [step][256 lanes] entries (the band's words fit in there)
-      k.j.ws_off = ws; ws += ((size_t)lb + 256) * 256 * align_coop_entry_bytes(k.R);
-      k.j.str_off = strs; strs += 2 * ((size_t)la + lb + 1);
-    } else if (k.family == KF_ALIGN) {
-      k.j.ws_off = ws; ws += ((size_t)lb + 64) * 64 * align_entry_bytes(k.R);
+    } else if (k.family == KF_ALIGN || k.family == KF_ALIGNB) {   // up to 64 rows: one wave; above: four waves,
+      // [step][256 lanes] entries (the band's words fit in there)
+      k.j.ws_off = ws; ws += k.R == 1 ? ((size_t)lb + 64) * 64 : ((size_t)lb + 256) * 256 * align_coop_entry_bytes(k.R);
       k.j.str_off = strs; strs += 2 * ((size_t)la + lb + 1);
     } else if (k.family == KF_GAP) {
       k.j.ws_off = ws; ws += ((size_t)lb + 64) * 64 * gap_entry_bytes(k.R);
@@ -576,11 +551,11 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
   i = 0;
   while (i < v.size()) {
     size_t j = i;
-    // a launch group = a family; BORDERS and AFFIX split into (up to 64 rows: one wave per job),
-    // (more rows: one job per workgroup) and, AFFIX only, (beyond 4096 rows: strips)
-    auto variant = [align_coop](const Keyed& k) -> int {
+    // a launch group = a family; BORDERS, AFFIX and ALIGN split into (up to 64 rows: one wave per job),
+    // (more rows: one job per workgroup) and (beyond 4096 rows: strips), GAP into (up to 2048 rows) and (more)
+    auto variant = [](const Keyed& k) -> int {
       if (k.family == KF_GAP) return k.R == ROW_CLASS_STRIPS ? (int)ROW_CLASS_STRIPS : 0;
-      if (k.family != KF_BORDERS && k.family != KF_AFFIX && !(k.family == KF_ALIGN && align_coop)) return 0;
+      if (k.family != KF_BORDERS && k.family != KF_AFFIX && k.family != KF_ALIGN) return 0;
       return k.R == 1 ? 1 : (k.R == ROW_CLASS_STRIPS ? (int)ROW_CLASS_STRIPS : 0);
     };
     Group g{};
@@ -621,8 +596,8 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
     else if (g.family == KF_AFFIX && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "lev_wave<AFFIX,strips>");
     else if (g.family == KF_BORDERS && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "borders_slow");
     else if (g.family == KF_GAP && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "gap_slow");
-    else if (g.family == KF_ALIGN && align_coop && g.R == 0) snprintf(nm, sizeof nm, "align_coop");
-    else if (g.family == KF_ALIGN && align_coop && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "lev_wave<ALIGN,strips>");
+    else if (g.family == KF_ALIGN && g.R == 0) snprintf(nm, sizeof nm, "align_coop");
+    else if (g.family == KF_ALIGN && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "lev_wave<ALIGN,strips>");
     else snprintf(nm, sizeof nm, "%s", fam[g.family]);
     g.name = nm;
     p->groups.push_back(g);
@@ -632,18 +607,21 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
     p->cells[g.kind] += g.cells;
     p->algo_bytes[g.kind] += g.algo_bytes;
   }
-  if (ctx->merged) {
-    // the common row classes of the wave-per-job families run in one launch (wave_jobs_kernel); the
-    // groups keep their BIG part (first n_big jobs).  Long-running families first.
-    static const int order_fam[9] = { KF_ALIGNB, KF_ALIGN, KF_GAP, KF_KBAND, KF_BORDERS, KF_AFFIX, KF_LCFSA, KF_LCFW, KF_ED };
+  {
+    // ONE launch (dp_batch_kernel) for the latency-bound part of the batch: the common row classes of the
+    // wave-per-job families, long-running families first (the groups keep their BIG part, the first n_big
+    // jobs), and the one-job-per-workgroup sweeps unless the largest BORDERS pattern needs more LDS than the
+    // roles may share
+    static constexpr int order_fam[9] = { KF_ALIGNB, KF_ALIGN, KF_GAP, KF_KBAND, KF_BORDERS, KF_AFFIX, KF_LCFSA, KF_LCFW, KF_ED };
+    static_assert(sizeof order_fam / sizeof order_fam[0] <= MAX_WAVE_SEGS, "one segment per family at most");
     Group m{};
-    m.family = KF_COUNT; m.kind = PGPU_DP_ALIGN; m.name = "wave_jobs";
+    m.family = KF_COUNT; m.kind = PGPU_DP_ALIGN; m.name = "dp_batch";
     for (int f : order_fam)
       for (auto& g : p->groups) {
-        if (g.family != f || g.traceback) continue;
-        const bool split = f == KF_BORDERS || f == KF_AFFIX || (f == KF_ALIGN && align_coop);   // one wave up to 64 rows, several above
+        if (g.family != f) continue;
+        const bool split = f == KF_BORDERS || f == KF_AFFIX || f == KF_ALIGN;   // one wave up to 64 rows, several above
         const bool wave_family = split ? g.R == 1 : g.R == 0;
-        if (!wave_family || p->n_segs >= MAX_WAVE_SEGS) continue;
+        if (!wave_family) continue;
         const size_t big = split ? 0 : g.n_big;
         if (g.count <= big) continue;
         p->seg_family[p->n_segs] = f; p->seg_start[p->n_segs] = (int)(g.first + big); p->seg_count[p->n_segs] = (int)(g.count - big);
@@ -653,26 +631,21 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
         g.in_merged = true;
         g.count = big; g.cells = big ? g.cells_big : 0; g.algo_bytes = big ? g.algo_big : 0;
       }
-    if (ctx->merged >= 2) {
-      // the one-job-per-workgroup sweeps join it (dp_batch_kernel) unless the largest BORDERS pattern
-      // needs more LDS than the roles may share
-      for (auto& g : p->groups) {
-        if (g.traceback || g.R != 0 || g.count == 0 || g.count > 0x3fffffffu) continue;
-        if (g.family == KF_BORDERS && dp_batch_lds_bytes(true, 1, g.max_rows, 1, 1) <= 64 * 1024) {
-          p->bc_start = (int)g.first; p->bc_count = (int)g.count; p->bc_max_rows = g.max_rows;
-        } else if (g.family == KF_AFFIX) {
-          p->ac_start = (int)g.first; p->ac_count = (int)g.count;
-        } else if (g.family == KF_ALIGN && align_coop) {
-          p->lc_start = (int)g.first; p->lc_count = (int)g.count;
-        } else continue;
-        m.count += g.count; m.cells += g.cells; m.algo_bytes += g.algo_bytes;
-        g.in_merged = true; g.count = 0; g.cells = 0; g.algo_bytes = 0;
-        p->batch = true;
-      }
-      if (p->n_segs) p->batch = true;
-      if (p->batch) m.name = "dp_batch";
+    bool coop = false;
+    for (auto& g : p->groups) {
+      if (g.R != 0 || g.count == 0) continue;
+      if (g.family == KF_BORDERS && dp_batch_lds_bytes(true, 1, g.max_rows, 1, 1) <= 64 * 1024) {
+        p->bc_start = (int)g.first; p->bc_count = (int)g.count; p->bc_max_rows = g.max_rows;
+      } else if (g.family == KF_AFFIX) {
+        p->ac_start = (int)g.first; p->ac_count = (int)g.count;
+      } else if (g.family == KF_ALIGN) {
+        p->lc_start = (int)g.first; p->lc_count = (int)g.count;
+      } else continue;
+      m.count += g.count; m.cells += g.cells; m.algo_bytes += g.algo_bytes;
+      g.in_merged = true; g.count = 0; g.cells = 0; g.algo_bytes = 0;
+      coop = true;
     }
-    if (p->n_segs || p->batch) { p->merged_group = (int)p->groups.size(); p->groups.push_back(m); }
+    if (p->n_segs || coop) p->groups.push_back(m);       // the pseudo group that carries its timing and accounting
   }
   if (ctx->timing) {
     const size_t need = 2 * p->groups.size();
@@ -758,29 +731,26 @@ extern "C" int pgpu_dp_plan_launch(pgpu_ctx* ctx, pgpu_dp_plan* p) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   p->synced = false; p->lcf_decoded = false;       // a relaunch downloads anew: the image holds raw keys again
   // Launch order: the groups are independent, and the host needs a few microseconds per launch, so
-  // the long poles go first (one-job-per-workgroup sweeps with many rows, then the alignments with
-  // their tracebacks, ...) and the thousands of tiny edit distances last.  A traceback group
-  // directly follows its DP group in p->groups and stays behind it on the same stream.
+  // the long poles go first: the batch launch, the one-job-per-workgroup sweeps it does not hold, the
+  // large alignments, ... and the large edit distances last.
   std::vector<size_t> order;
   std::vector<size_t> key_of(p->groups.size(), 0);
   {
     size_t kb = 0;
     for (size_t gi = 0; gi < p->groups.size(); ++gi) {
       const Group& g = p->groups[gi];
-      if (g.traceback) continue;
       if (g.family == KF_LCF) { key_of[gi] = kb; kb += g.count; }
-      if (g.in_merged && g.count == 0) continue;           // nothing left outside the merged launch
+      if (g.in_merged && g.count == 0) continue;           // nothing left outside the batch launch
       order.push_back(gi);
     }
     auto weight = [&](size_t gi) -> long {
       const Group& g = p->groups[gi];
       switch (g.family) {
-        case KF_COUNT: return p->batch ? 20000 : 9000;    // the merged launch: behind the one-job-per-workgroup poles it does not hold
-        case KF_BORDERS: case KF_AFFIX: return g.R == 1 ? 150 : 10000 + (long)g.max_rows;
-        case KF_ALIGN: if (g.name == "align_coop") return 9000 + (long)g.max_rows; return 5000;
+        case KF_COUNT: return 20000;
+        case KF_BORDERS: case KF_AFFIX: return 10000 + (long)g.max_rows;
+        case KF_ALIGN: return 5000;
         case KF_GAP: return 4000;
         case KF_LCF: return 3000;
-        case KF_LCFSA: case KF_LCFW: return 2500;
         case KF_KBAND: return 2000;
         default: return 1000;
       }
@@ -788,27 +758,20 @@ extern "C" int pgpu_dp_plan_launch(pgpu_ctx* ctx, pgpu_dp_plan* p) {
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weight(a) > weight(b); });
   }
   // HIP spreads its streams over four hardware queues, and what shares a queue runs one after the
-  // other.  Packed: four streams (one per queue), the families dealt out so that the four sums of
-  // typical durations come out even; the batch launch stays on the main stream (lane -1), where the
-  // upload already is, and only the streams a plan uses are forked and joined.  Otherwise
-  // round-robin in launch order.
+  // other: four streams (one per queue), the families dealt out so that the four sums of typical
+  // durations come out even; the batch launch stays on the main stream (lane -1), where the upload
+  // already is, and only the streams a plan uses are forked and joined.
   std::vector<int> lane_of(order.size(), 0);
   unsigned used_mask = 0;
   for (size_t oi = 0; oi < order.size(); ++oi) {
-    const Group& g = p->groups[order[oi]];
-    int l = (int)(oi % (size_t)ctx->n_aux);
-    if (ctx->packed) {
-      const bool one_wave = g.R == 1;          // BORDERS / AFFIX with up to 64 rows
-      switch (g.family) {
-        case KF_AFFIX:   l = one_wave ? 1 : 0; break;
-        case KF_BORDERS: l = one_wave ? 0 : 1; break;
-        case KF_ED:      l = 1; break;
-        case KF_COUNT:   l = p->batch ? -1 : 2; break;
-        case KF_ALIGN: case KF_KBAND: l = 2; break;
-        default: l = 3; break;           // GAP, LCF
-      }
+    int l;
+    switch (p->groups[order[oi]].family) {
+      case KF_AFFIX:   l = 0; break;
+      case KF_BORDERS: case KF_ED: l = 1; break;
+      case KF_COUNT:   l = -1; break;
+      case KF_ALIGN: case KF_KBAND: l = 2; break;
+      default: l = 3; break;           // GAP, LCF
     }
-    if (!ctx->fanout) l = -1;
     lane_of[oi] = l;
     if (l >= 0) used_mask |= 1u << l;
   }
@@ -821,53 +784,37 @@ extern "C" int pgpu_dp_plan_launch(pgpu_ctx* ctx, pgpu_dp_plan* p) {
       }
   }
   for (size_t oi = 0; oi < order.size(); ++oi) {
-    for (size_t gi = order[oi]; gi < p->groups.size() && (gi == order[oi] || p->groups[gi].traceback); ++gi) {
-      Group& g = p->groups[gi];
-      const DevJob* jobs = p->d_jobs + g.first;
-      const int n = (int)g.count;
-      hipStream_t st = lane_of[oi] >= 0 ? ctx->aux[lane_of[oi]] : ctx->stream;
-      if (g.ev0) HIP_TRY(ctx, hipEventRecord(g.ev0, st));
-      g.launched = true;
-      pgpu_range_push(g.name.c_str());
-      struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
-      switch (g.family) {
-        case KF_COUNT:
-          if (p->batch) {
-            if (!launch_dp_batch(p->d_jobs, p->n_segs, p->seg_family, p->seg_start, p->seg_count, p->bc_start, p->bc_count,
-                                 p->bc_max_rows, p->ac_start, p->ac_count, p->lc_start, p->lc_count, p->d_results, p->d_ws, p->d_strs, p->lcf_ix, st))
-              return set_err(ctx, PGPU_EDEVICE, "batch launch: LDS budget exceeded");
-          } else {
-            launch_wave_jobs(p->d_jobs, p->n_segs, p->seg_family, p->seg_start, p->seg_count, p->d_results, p->d_ws, p->d_strs, p->lcf_ix, st);
-          }
-          break;
-        case KF_ALIGN: case KF_ED: case KF_BORDERS: case KF_AFFIX: case KF_KBAND:
-          launch_lev(g.family, g.R, g.max_rows, jobs, n, (int)g.n_big, p->d_results, p->d_ws, p->d_strs, st); break;
-        case KF_GAP:
-          if (g.R == (int)ROW_CLASS_STRIPS) launch_gap_slow(jobs, n, p->d_results, p->d_ws, p->d_strs, st);
-          else launch_gap(jobs, n, (int)g.n_big, p->d_results, p->d_ws, p->d_strs, st);
-          break;
-        case KF_LCF:
-          launch_lcf(jobs, n, g.max_chunks, g.max_l2, p->d_keys + key_of[gi], st);
-          break;
-        case KF_ALIGNB: {                     // (only when the merged launch had no segment left for it)
-          const int fam1 = g.family, start1 = (int)g.first, count1 = n;
-          launch_wave_jobs(p->d_jobs, 1, &fam1, &start1, &count1, p->d_results, p->d_ws, p->d_strs, p->lcf_ix, st);
-          launch_align_fallback(jobs, n, p->d_results, p->d_ws, p->d_strs, st);
-          break;
-        }
-        case KF_LCFSA: case KF_LCFW: {       // a launch of their own only with PGPU_MERGED=0
-          const int fam1 = g.family, start1 = (int)g.first, count1 = n;
-          launch_wave_jobs(p->d_jobs, 1, &fam1, &start1, &count1, p->d_results, p->d_ws, p->d_strs, p->lcf_ix, st);
-          break;
-        }
-        default: break;
-      }
-      if (g.ev1) HIP_TRY(ctx, hipEventRecord(g.ev1, st));
-      // behind the merged launch (and outside its pair of events, which time the one kernel the profiler lists as
-      // dp_batch_kernel): the whole-matrix sweep of the banded alignments it could not settle
-      if (g.family == KF_COUNT) launch_align_fallback(p->d_jobs + p->ab_start, p->ab_count, p->d_results, p->d_ws, p->d_strs, st);
-      HIP_TRY(ctx, hipGetLastError());
+    const size_t gi = order[oi];
+    Group& g = p->groups[gi];
+    const DevJob* jobs = p->d_jobs + g.first;
+    const int n = (int)g.count;
+    hipStream_t st = lane_of[oi] >= 0 ? ctx->aux[lane_of[oi]] : ctx->stream;
+    if (g.ev0) HIP_TRY(ctx, hipEventRecord(g.ev0, st));
+    g.launched = true;
+    pgpu_range_push(g.name.c_str());
+    struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
+    switch (g.family) {
+      case KF_COUNT:
+        if (!launch_dp_batch(p->d_jobs, p->n_segs, p->seg_family, p->seg_start, p->seg_count, p->bc_start, p->bc_count,
+                             p->bc_max_rows, p->ac_start, p->ac_count, p->lc_start, p->lc_count, p->d_results, p->d_ws, p->d_strs, p->lcf_ix, st))
+          return set_err(ctx, PGPU_EDEVICE, "batch launch: LDS budget exceeded");
+        break;
+      case KF_ALIGN: case KF_ED: case KF_BORDERS: case KF_AFFIX: case KF_KBAND:
+        launch_lev(g.family, g.R, g.max_rows, jobs, n, p->d_results, p->d_ws, p->d_strs, st); break;
+      case KF_GAP:
+        if (g.R == (int)ROW_CLASS_STRIPS) launch_gap_slow(jobs, n, p->d_results, p->d_ws, p->d_strs, st);
+        else launch_gap(jobs, n, p->d_results, p->d_ws, p->d_strs, st);
+        break;
+      case KF_LCF:
+        launch_lcf(jobs, n, g.max_chunks, g.max_l2, p->d_keys + key_of[gi], st);
+        break;
+      default: break;
     }
+    if (g.ev1) HIP_TRY(ctx, hipEventRecord(g.ev1, st));
+    // behind the batch launch (and outside its pair of events, which time the one kernel the profiler lists as
+    // dp_batch_kernel): the whole-matrix sweep of the banded alignments it could not settle
+    if (g.family == KF_COUNT) launch_align_fallback(p->d_jobs + p->ab_start, p->ab_count, p->d_results, p->d_ws, p->d_strs, st);
+    HIP_TRY(ctx, hipGetLastError());
   }
   for (int i = 0; i < pgpu_ctx::NAUX; ++i) {      // join: the main stream continues after every stream that was used
     if (!(used_mask & (1u << i))) continue;
@@ -906,7 +853,7 @@ extern "C" int pgpu_dp_plan_sync(pgpu_ctx* ctx, pgpu_dp_plan* p) {
     for (int k = 0; k < PGPU_DP_NKINDS; ++k) { p->ms[k] = 0; p->launches[k] = 0; }
     for (auto& g : p->groups) {
       float ms = 0.f;
-      if (!g.launched) continue;            // everything of this group ran inside the merged launch
+      if (!g.launched) continue;            // everything of this group ran inside the batch launch
       if (g.ev0 && g.ev1 && hipEventElapsedTime(&ms, g.ev0, g.ev1) == hipSuccess) g.ms = ms;
       if (g.ev0) { hipEvent_t b = base_event(ctx->device, ctx->stream); float t0 = 0.f; g.t0_ms = (b && hipEventElapsedTime(&t0, b, g.ev0) == hipSuccess) ? t0 : -1.f; }
       p->ms[g.kind] += g.ms;

@@ -557,10 +557,8 @@ __device__ __forceinline__ void lev_wave_body(const DevJob& job, DevResult* res,
     store_row_value<R>(cur, lane, n, &res->v[0]);
     if (lane == 0) { res->status = 0; res->v[5] = 0; }
   } else if constexpr (MODE == MODE_BORDERS) {
-    // pre[], pre_pos[], suf[], suf_pos[], each len_p+1: the wave's own LDS region when the caller
-    // hands one in (several jobs per workgroup), else the workgroup's dynamic LDS
-    extern __shared__ uint32_t lds_dyn[];
-    uint32_t* lds = wave_lds ? wave_lds : lds_dyn;
+    // pre[], pre_pos[], suf[], suf_pos[], each len_p+1: the wave's own LDS region (several jobs per workgroup)
+    uint32_t* lds = wave_lds;
     const uint32_t len_p = job.la, len_t = job.lb, max_errs = job.p2;
     const uint32_t t_win = min(len_p + max_errs, len_t);
     uint32_t* pre = lds; uint32_t* pre_pos = pre + (len_p + 1);
@@ -702,20 +700,19 @@ __device__ __forceinline__ void lev_wave_body(const DevJob& job, DevResult* res,
   }
 }
 
-// one row class per launch (BORDERS with up to 64 rows, AFFIX with up to 64 rows or in strips)
+// one row class per launch (AFFIX beyond 4096 rows, in strips)
 template <int R, int MODE, bool STRIPS = false>
-__global__ __launch_bounds__(MODE == MODE_BORDERS ? 64 : 256)
+__global__ __launch_bounds__(256)
 void lev_wave_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __restrict__ results,
                      uint8_t* __restrict__ ws) {
-  constexpr int WAVES = MODE == MODE_BORDERS ? 1 : 4;
   const uint32_t lane = threadIdx.x & 63u;
-  const int w = blockIdx.x * WAVES + (threadIdx.x >> 6);
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= njobs) return;
   const DevJob job = jobs[w];
   lev_wave_body<R, MODE, STRIPS>(job, &results[job.out_idx], ws, lane);
 }
 
-// ALL row classes of a family in ONE launch: the jobs of a merged batch are few per class, and
+// ALL row classes of a family in ONE launch: the jobs of a batch are few per class, and
 // kernels of one stream or hardware queue run one after the other, so a launch per class costs
 // the sum of the classes' longest jobs; in one launch they overlap.  Every wave picks the body of
 // its job's class (jobs are sorted by class, so the waves of a workgroup mostly agree).
@@ -739,9 +736,9 @@ __device__ __forceinline__ void own_stores_visible() {
 }
 
 // BIG = the classes with 32 and 64 rows per lane and the strips (rare in a batch, a few hundred
-// registers per lane); the common classes up to 16 rows per lane get a kernel of their own whose
-// register budget lets several waves share a SIMD.  Jobs are sorted big classes first, so the two
-// launches take the two ends of the family's slice.
+// registers per lane): they get a kernel of their own (lev_any_kernel), and the common classes up to
+// 16 rows per lane run inside dp_batch_kernel, whose register budget lets several waves share a SIMD.
+// Jobs are sorted big classes first, so the two take the two ends of the family's slice.
 template <int MODE, bool BIG>
 __device__ __forceinline__ void lev_any_dispatch(const DevJob& job, DevResult* res, uint8_t* __restrict__ ws, const uint32_t lane) {
   if constexpr (BIG) {
@@ -761,7 +758,7 @@ __device__ __forceinline__ void lev_any_dispatch(const DevJob& job, DevResult* r
   }
 }
 
-template <int MODE, bool BIG>
+template <int MODE>
 __global__ __launch_bounds__(256)
 void lev_any_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __restrict__ results,
                     uint8_t* __restrict__ ws, uint8_t* __restrict__ strs) {
@@ -770,7 +767,7 @@ void lev_any_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __res
   if (w >= njobs) return;
   const DevJob job = jobs[w];
   DevResult* res = &results[job.out_idx];
-  lev_any_dispatch<MODE, BIG>(job, res, ws, lane);
+  lev_any_dispatch<MODE, true>(job, res, ws, lane);
   if constexpr (MODE == MODE_ALIGN) {      // matrix, then the traceback by the same wave
     __shared__ __attribute__((aligned(16))) uint8_t s_win[4][TB_WIN_BYTES];
     __shared__ uint8_t s_path[4][TB_PATH];
@@ -1011,14 +1008,6 @@ __device__ __forceinline__ void affix_coop_dispatch(const DevJob& job, DevResult
   }
 }
 
-__global__ __launch_bounds__(256)
-void affix_coop_any_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __restrict__ results) {
-  __shared__ uint32_t hand[(COOP_W - 1) * 128];
-  __shared__ uint32_t wbest[COOP_W][5];
-  const DevJob job = jobs[blockIdx.x];
-  affix_coop_dispatch(job, &results[job.out_idx], hand, wbest);
-}
-
 // TracebackAlignment (src/compute-alignments.c:149-207), one WAVE per job.
 // The walk from (n,m) back to the border is a chain of dependent direction look-ups; done by one
 // thread against HBM/L2 every step costs a memory round trip (~250 ns).  Here the wave copies a
@@ -1213,9 +1202,6 @@ __device__ __forceinline__ void align_traceback_coop(const DevJob& job, DevResul
 // whole matrix.  Directions: 2 bits per cell, one 32-bit word per lane and 16 rows, [row / 16][lane].
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t ALIGN_BAND_K = ALIGN_BAND_HALF;
-__device__ __forceinline__ bool align_band_fits(uint32_t n, uint32_t m) {
-  return n > 0u && m > 0u && (n > m ? n - m : m - n) <= ALIGN_BAND_K;
-}
 
 // returns the banded M[n][m] in every lane; dirs: ((n >> 4) + 1) * 64 words
 __device__ __noinline__ uint32_t align_band_sweep(const uint8_t* __restrict__ a, const uint32_t n,
@@ -1352,24 +1338,6 @@ __device__ __forceinline__ void align_coop_body(const DevJob& job, DevResult* re
     align_traceback_wave(job, res, ws, strs, lane, win, path);      // its identity branch
     return;
   }
-  // first inside a band on wave 0 (job.tail: the host's switch); the other waves wait for its verdict
-  if (job.tail != 0u && align_band_fits(n, m)) {
-    uint32_t* bdirs = reinterpret_cast<uint32_t*>(ws + job.ws_off);
-    if (w == 0) {
-      const uint32_t score = align_band_sweep(job.a, n, job.b, m, lane, bdirs);
-      if (lane == 0) hand[0] = score;
-    }
-    __syncthreads();
-    const uint32_t score = hand[0];
-    __syncthreads();                     // (hand is the sweep's hand-off buffer below)
-    if (score <= ALIGN_BAND_K) {
-      if (w != 0) return;
-      if (lane == 0) { res->status = 0; res->v[0] = (int32_t)score; res->v[5] = 0; }
-      own_stores_visible();
-      align_band_traceback(job, res, bdirs, strs, lane, win, path);
-      return;
-    }
-  }
   uint32_t cur[R], minv[R], minpos[R];
   AffixBest best = AFFIX_NONE;
   const Operand rows{job.a, 0, false}, cols{job.b, 0, false};
@@ -1397,14 +1365,6 @@ __device__ __forceinline__ void align_coop_dispatch(const DevJob& job, DevResult
     case 32: align_coop_body<8>(job, res, ws, strs, smem); break;
     default: align_coop_body<16>(job, res, ws, strs, smem); break;
   }
-}
-
-__global__ __launch_bounds__(256)
-void align_coop_any_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __restrict__ results,
-                           uint8_t* __restrict__ ws, uint8_t* __restrict__ strs) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[ALIGN_COOP_LDS];
-  const DevJob job = jobs[blockIdx.x];
-  align_coop_dispatch(job, &results[job.out_idx], ws, strs, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1509,9 +1469,8 @@ __device__ __forceinline__ void gap_wave_body(const DevJob& job, DevResult* res,
   }
 }
 
-// all row classes of a batch's gap alignments in one launch (see lev_any_kernel); BIG = 8 rows per
-// lane and more (gap alignments of more than 256 EST characters: rare)
-template <bool BIG>
+// the large row classes of a batch's gap alignments in one launch (see lev_any_kernel): 8 rows per lane
+// and more (gap alignments of more than 256 EST characters: rare); the others run inside dp_batch_kernel
 __global__ __launch_bounds__(256)
 void gap_any_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __restrict__ results,
                     uint8_t* __restrict__ ws, uint8_t* __restrict__ strs) {
@@ -1522,18 +1481,10 @@ void gap_any_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __res
   if (w >= njobs) return;
   const DevJob job = jobs[w];
   DevResult* res = &results[job.out_idx];
-  if constexpr (BIG) {
-    switch (job.r_class) {
-      case 8:  gap_wave_body<8>(job, res, ws, lane); break;
-      case 16: gap_wave_body<16>(job, res, ws, lane); break;
-      default: gap_wave_body<32>(job, res, ws, lane); break;
-    }
-  } else {
-    switch (job.r_class) {
-      case 1:  gap_wave_body<1>(job, res, ws, lane); break;
-      case 2:  gap_wave_body<2>(job, res, ws, lane); break;
-      default: gap_wave_body<4>(job, res, ws, lane); break;
-    }
+  switch (job.r_class) {
+    case 8:  gap_wave_body<8>(job, res, ws, lane); break;
+    case 16: gap_wave_body<16>(job, res, ws, lane); break;
+    default: gap_wave_body<32>(job, res, ws, lane); break;
   }
   own_stores_visible();                  // the planes and the start plane (res->pad)
   gap_traceback_wave(job, res, ws, strs, lane, s_win[threadIdx.x >> 6], s_path[threadIdx.x >> 6]);
@@ -1914,7 +1865,7 @@ __device__ __forceinline__ void endpoint_epilogue(const DevJob& job, DevResult* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// ONE launch for every wave-per-job family of a batch.  A merged batch used to cost eleven launches
+// ONE launch for every wave-per-job family of a batch (the wave-job role of dp_batch_kernel).  A batch used to cost eleven launches
 // dealt onto four hardware queues, and the kernels of a queue run one after the other: the batch
 // took the SUM of its families' long poles per queue.  Here every wave of the grid looks its job up
 // in a short segment table (family, first job, count; long-running families first) and runs that
@@ -1945,8 +1896,8 @@ __device__ __forceinline__ void wave_jobs_body(const int block, const int wave, 
   const DevJob job = jobs[idx];
   DevResult* res = &results[job.out_idx];
   switch (fam) {
-    case KF_ALIGN:
-      lev_any_dispatch<MODE_ALIGN, false>(job, res, ws, lane);
+    case KF_ALIGN:                       // up to 64 rows (the rest are on four waves: align_coop_body)
+      lev_wave_body<1, MODE_ALIGN>(job, res, ws, lane);
       own_stores_visible();
       align_traceback_wave(job, res, ws, strs, lane, s_win, s_path);
       if (job.p0 != 0u) { own_stores_visible(); endpoint_epilogue(job, res, strs, ws, lane, reinterpret_cast<DevResult*>(s_borders)); }
@@ -1990,24 +1941,15 @@ __device__ __forceinline__ void wave_jobs_body(const int block, const int wave, 
   }
 }
 
-// follow-up of the merged launch: the banded ALIGN jobs whose score exceeded the band, on four waves each;
+// follow-up of the batch launch: the banded ALIGN jobs whose score exceeded the band, on four waves each;
 // a workgroup whose job is settled (nearly all) ends at once
 __global__ __launch_bounds__(256)
 void align_fallback_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* __restrict__ results,
                            uint8_t* __restrict__ ws, uint8_t* __restrict__ strs) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[ALIGN_COOP_LDS];
-  DevJob job = jobs[blockIdx.x];
+  const DevJob job = jobs[blockIdx.x];
   if (results[job.out_idx].status != ALIGN_BAND_RETRY) return;
-  job.tail = 0;                          // the band has been tried
   align_coop_dispatch(job, &results[job.out_idx], ws, strs, smem);
-}
-
-__global__ __launch_bounds__(256)
-void wave_jobs_kernel(const DevJob* __restrict__ jobs, const WaveSegs segs, DevResult* __restrict__ results,
-                      uint8_t* __restrict__ ws, uint8_t* __restrict__ strs, const LcfIndexView ix) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[WAVE_JOBS_LDS];
-  const int wave = (int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  wave_jobs_body((int)blockIdx.x, wave, threadIdx.x & 63u, jobs, segs, results, ws, strs, smem, ix);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2281,46 +2223,26 @@ void borders_slow_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* 
 
 }  // namespace
 
-// R = 0: every row class of the family in one launch (ED, ALIGN, KBAND: the first n_big jobs are
-// of the classes above 16 rows per lane and go to the BIG instance; BORDERS / AFFIX above 64
-// rows, `max_rows` sizes the dynamic LDS); R = 1: the single-wave BORDERS / AFFIX kernels;
-// R = ROW_CLASS_STRIPS: AFFIX beyond 4096 rows.
-template <int MODE>
-static void launch_lev_any(const DevJob* jobs, int njobs, int n_big, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st) {
-  const dim3 b256(256);
-  if (n_big > 0)
-    hipLaunchKernelGGL((lev_any_kernel<MODE, true>), dim3((n_big + 3) / 4), b256, 0, st, jobs, n_big, res, ws, strs);
-  if (njobs > n_big)
-    hipLaunchKernelGGL((lev_any_kernel<MODE, false>), dim3((njobs - n_big + 3) / 4), b256, 0, st, jobs + n_big, njobs - n_big, res, ws, strs);
-}
-
-void launch_lev(int family, int R, uint32_t max_rows, const DevJob* jobs, int njobs, int n_big, DevResult* res, uint8_t* ws,
+// What dp_batch_kernel leaves to launches of their own: ED, ALIGN, KBAND of the large row classes (all of
+// them BIG: see lev_any_dispatch), BORDERS above 64 rows whose LDS exceeds the batch's (R = 0, `max_rows`
+// sizes the dynamic LDS) or beyond 4096 rows, AFFIX beyond 4096 rows (R = ROW_CLASS_STRIPS).
+void launch_lev(int family, int R, uint32_t max_rows, const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws,
                 uint8_t* strs, hipStream_t st) {
   if (njobs <= 0) return;
   const dim3 g4((njobs + 3) / 4), b256(256);
   switch (family) {
-    case KF_ED:    launch_lev_any<MODE_ED>(jobs, njobs, n_big, res, ws, strs, st); break;
-    case KF_ALIGN:
-      if (R == 0) hipLaunchKernelGGL(align_coop_any_kernel, dim3(njobs), dim3(256), 0, st, jobs, njobs, res, ws, strs);   // 65 .. 4096 rows
-      else launch_lev_any<MODE_ALIGN>(jobs, njobs, n_big, res, ws, strs, st);
-      break;
-    case KF_KBAND: launch_lev_any<MODE_KBAND>(jobs, njobs, n_big, res, ws, strs, st); break;
+    case KF_ED:    hipLaunchKernelGGL(lev_any_kernel<MODE_ED>, g4, b256, 0, st, jobs, njobs, res, ws, strs); break;
+    case KF_ALIGN: hipLaunchKernelGGL(lev_any_kernel<MODE_ALIGN>, g4, b256, 0, st, jobs, njobs, res, ws, strs); break;
+    case KF_KBAND: hipLaunchKernelGGL(lev_any_kernel<MODE_KBAND>, g4, b256, 0, st, jobs, njobs, res, ws, strs); break;
     case KF_BORDERS:
-      if (R == 1) {
-        const size_t lds = 4 * (64 + 1) * sizeof(uint32_t);
-        hipLaunchKernelGGL((lev_wave_kernel<1, MODE_BORDERS>), dim3(njobs), dim3(64), lds, st, jobs, njobs, res, ws);
-      } else if (R == (int)ROW_CLASS_STRIPS) {
+      if (R == (int)ROW_CLASS_STRIPS) {
         hipLaunchKernelGGL(borders_slow_kernel, dim3(njobs), dim3(SLOW_BLOCK), 0, st, jobs, njobs, res, ws);
       } else {
         const size_t lds = (2 * (COOP_W - 1) * 128 + 4 * ((size_t)max_rows + 1)) * sizeof(uint32_t);
         hipLaunchKernelGGL(borders_coop_any_kernel, dim3(njobs), dim3(512), lds, st, jobs, njobs, res);
       }
       break;
-    case KF_AFFIX:
-      if (R == 1) hipLaunchKernelGGL((lev_wave_kernel<1, MODE_AFFIX>), g4, b256, 0, st, jobs, njobs, res, ws);
-      else if (R == (int)ROW_CLASS_STRIPS) hipLaunchKernelGGL((lev_wave_kernel<64, MODE_AFFIX, true>), g4, b256, 0, st, jobs, njobs, res, ws);
-      else hipLaunchKernelGGL(affix_coop_any_kernel, dim3(njobs), dim3(256), 0, st, jobs, njobs, res);
-      break;
+    case KF_AFFIX: hipLaunchKernelGGL((lev_wave_kernel<64, MODE_AFFIX, true>), g4, b256, 0, st, jobs, njobs, res, ws); break;
     default: break;
   }
 }
@@ -2330,32 +2252,14 @@ void launch_align_fallback(const DevJob* jobs, int njobs, DevResult* res, uint8_
   hipLaunchKernelGGL(align_fallback_kernel, dim3(njobs), dim3(256), 0, st, jobs, njobs, res, ws, strs);
 }
 
-// segments: (family, first job, count) of the jobs the merged kernel runs, long poles first
-void launch_wave_jobs(const DevJob* jobs, int n_segs, const int* family, const int* start, const int* count,
-                      DevResult* res, uint8_t* ws, uint8_t* strs, const LcfIndexView& ix, hipStream_t st) {
-  WaveSegs sg;
-  sg.n = 0;
-  int total = 0;
-  for (int k = 0; k < n_segs && sg.n < MAX_WAVE_SEGS; ++k) {
-    if (count[k] <= 0) continue;
-    sg.family[sg.n] = family[k]; sg.start[sg.n] = start[k]; sg.count[sg.n] = count[k]; ++sg.n;
-    total += count[k];
-  }
-  if (total == 0) return;
-  hipLaunchKernelGGL(wave_jobs_kernel, dim3((total + 3) / 4), dim3(256), 0, st, jobs, sg, res, ws, strs, ix);
-}
-
 void launch_gap_slow(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st) {
   if (njobs <= 0) return;
   hipLaunchKernelGGL(gap_slow_kernel, dim3(njobs), dim3(SLOW_BLOCK), 0, st, jobs, njobs, res, ws, strs);
 }
 
-void launch_gap(const DevJob* jobs, int njobs, int n_big, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st) {
+void launch_gap(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st) {
   if (njobs <= 0) return;
-  if (n_big > 0)
-    hipLaunchKernelGGL(gap_any_kernel<true>, dim3((n_big + 3) / 4), dim3(256), 0, st, jobs, n_big, res, ws, strs);
-  if (njobs > n_big)
-    hipLaunchKernelGGL(gap_any_kernel<false>, dim3((njobs - n_big + 3) / 4), dim3(256), 0, st, jobs + n_big, njobs - n_big, res, ws, strs);
+  hipLaunchKernelGGL(gap_any_kernel, dim3((njobs + 3) / 4), dim3(256), 0, st, jobs, njobs, res, ws, strs);
 }
 
 void launch_lcf(const DevJob* jobs, int njobs, uint32_t max_chunks, uint32_t max_l2,
@@ -2402,8 +2306,7 @@ bool launch_dp_batch(const DevJob* jobs, int n_segs, const int* family, const in
   d.ac_start = ac_start; d.ac_count = ac_count > 0 ? ac_count : 0;
   const int blocks = d.bc_count + d.ac_count + d.lc_count + d.wave_blocks;
   if (blocks == 0) return true;
-  static const size_t lds_pad = [] { const char* e = getenv("PGPU_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();   // measurement only
-  const size_t lds = dp_batch_lds_bytes(total > 0, d.bc_count, bc_max_rows, d.ac_count, d.lc_count) + lds_pad;
+  const size_t lds = dp_batch_lds_bytes(total > 0, d.bc_count, bc_max_rows, d.ac_count, d.lc_count);
   if (lds > DP_BATCH_MAX_LDS) return false;
   hipLaunchKernelGGL(dp_batch_kernel, dim3(blocks), dim3(512), lds, st, jobs, d, res, ws, strs);
   return true;

@@ -564,13 +564,12 @@ static hipError_t build_lcf_tables(pgpu_index* idx, const char* genomic, hipStre
   for (uint32_t i = 0; i < n; ++i) { const char c = genomic[i]; if (c != 'A' && c != 'C' && c != 'G' && c != 'T') { fb = i; break; } }
   idx->first_bad = fb;
   // The tables of the suffix-array LCF are optional: floor(log2 n) x n x 4 B of range minima is 14 MB for a 200 kb
-  // gene but 10 GB for 100 Mb.  Without them (switched off, a sequence beyond PGPU_LCF_SA_MAX_BASES -- default
-  // 2^26 --, or no memory) every LCF job takes lcf_kernel: pgpu_dp_plan_create_parts looks at d_focc / d_rmq.
+  // gene but 10 GB for 100 Mb.  Without them (a sequence beyond PGPU_LCF_SA_MAX_BASES -- default 2^26 --, or no
+  // memory) every LCF job takes lcf_kernel: pgpu_dp_plan_create_parts looks at d_focc / d_rmq.
   {
-    const char* sw = getenv("PGPU_LCF_SA");
     const char* mx = getenv("PGPU_LCF_SA_MAX_BASES");
     const unsigned long long max_bases = mx && atoll(mx) > 0 ? (unsigned long long)atoll(mx) : (1ull << 26);
-    if ((sw && sw[0] == '0' && sw[1] == '\0') || n > max_bases) return hipSuccess;
+    if (n > max_bases) return hipSuccess;
   }
   hipError_t e = hipMalloc((void**)&idx->d_focc, LCF_FOCC_ENTRIES * sizeof(uint32_t));
   if (e != hipSuccess) { idx->d_focc = nullptr; (void)hipGetLastError(); return hipSuccess; }

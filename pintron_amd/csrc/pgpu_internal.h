@@ -33,18 +33,17 @@ enum KernelFamily {
   KF_COUNT
 };
 
-// launchers (pgpu_dp_kernels.hip)
-void launch_lev(int mode_family, int R, uint32_t max_rows, const DevJob* jobs, int njobs, int n_big, DevResult* res,
+// launchers (pgpu_dp_kernels.hip) of what the batch launch leaves out: the large row classes, the strips and
+// BORDERS jobs whose LDS exceeds the batch's
+void launch_lev(int mode_family, int R, uint32_t max_rows, const DevJob* jobs, int njobs, DevResult* res,
                 uint8_t* ws, uint8_t* strs, hipStream_t st);     // ALIGN: matrix + traceback
-void launch_gap(const DevJob* jobs, int njobs, int n_big, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st);   // + traceback
+void launch_gap(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st);   // + traceback
 void launch_gap_slow(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st);   // beyond 2048 rows
 constexpr int MAX_WAVE_SEGS = 10;
 constexpr int32_t ALIGN_BAND_RETRY = 1;     // DevResult.status of a banded ALIGN that has to be swept in full (never leaves the library)
 constexpr uint32_t ALIGN_BAND_HALF = 31u;   // half-width of the band (2k + 1 <= 64 lanes)
 // the whole-matrix sweep (four waves per job) for the jobs of [jobs, jobs + njobs) the band could not settle
 void launch_align_fallback(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st);
-void launch_wave_jobs(const DevJob* jobs, int n_segs, const int* family, const int* start, const int* count,
-                      DevResult* res, uint8_t* ws, uint8_t* strs, const LcfIndexView& ix, hipStream_t st);   // every wave-per-job family in one launch
 // one launch for the one-job-per-workgroup sweeps and the wave-per-job families of a batch; returns
 // false (nothing launched) when the largest BORDERS pattern needs more LDS than a workgroup may share
 bool launch_dp_batch(const DevJob* jobs, int n_segs, const int* family, const int* start, const int* count,

@@ -328,13 +328,11 @@ def test_align_inside_a_band(gpu_ctx, O):
     run_and_check(gpu_ctx, O, cases)
 
 
-def test_results_to_device_and_launch_modes(gpu_ctx, O):
+def test_results_to_device(gpu_ctx, O):
     """pgpu_dp_plan_results_to_device hands the COMPLETE table to device memory (the LCF answers are
-    decoded on the host from the kernel's keys); and the three launch modes of the library (PGPU_MERGED
-    = 2: one batch launch + LCF, 1: wave-per-job launch + sweeps, 0: a launch per family) give the same
-    answers for a batch that holds every family, one-job-per-workgroup sweeps included."""
+    decoded on the host from the kernel's keys), for a batch that holds every family, one-job-per-workgroup
+    sweeps included; and every answer agrees with the oracle."""
     import ctypes as C
-    import os
     import pintron_amd.capi as capi
     rng = random.Random(31)
     cases = D.random_cases(rng, n_per_kind=12, max_len=200)
@@ -368,21 +366,13 @@ def test_results_to_device_and_launch_modes(gpu_ctx, O):
     assert hip.hipMemcpy(back, dev, C.c_size_t(nbytes), 2) == 0          # hipMemcpyDeviceToHost
     hip.hipFree(dev)
     assert back.raw == bytes(res)[:nbytes]
-    base = [capi.decode(c.kind, r, strs) for c, r in zip(cases, res)]
-    for c, got in zip(cases, base):
+    answers = [capi.decode(c.kind, r, strs) for c, r in zip(cases, res)]
+    for c, got in zip(cases, answers):
         assert D.check_case(c, got, O), (c, got)
-    for mode in ("1", "0"):
-        os.environ["PGPU_MERGED"] = mode
-        try:
-            with capi.Context(0) as ctx2:
-                out = capi.run_jobs(ctx2, jl)
-        finally:
-            del os.environ["PGPU_MERGED"]
-        assert out == base, "PGPU_MERGED=%s differs" % mode
 
 
-@pytest.mark.parametrize("merged", ["2", "1", "0"])
-def test_lcf_from_the_suffix_array(O, merged, monkeypatch):
+@pytest.mark.parametrize("case_set", [2, 1, 0])
+def test_lcf_from_the_suffix_array(O, case_set):
     """find_longest_common_factor_dp of a genomic PREFIX against at most 64 EST characters, answered from
     the resident suffix array (lcfsa_wave_body) instead of the 46 x |prefix| matrix: same length, same first
     maximum (smallest start in the genomic, then in the EST) as the oracle on random sequences, planted
@@ -390,10 +380,9 @@ def test_lcf_from_the_suffix_array(O, merged, monkeypatch):
     minima decide), tiny alphabets, prefixes that cut an occurrence, empty operands; an EST prefix with ONE N
     (upper or lower case) is answered there too -- the four strings with A, C, G, T in its place -- and the jobs
     that do not qualify (two Ns, an N in the genomic prefix, more than 64 characters, a prefix beyond the first
-    non-ACGT character) still get the matrix kernel's answer.  In every launch mode of the library."""
+    non-ACGT character) still get the matrix kernel's answer.  Three case sets (seeds 77 .. 79)."""
     import pintron_amd.capi as capi
-    monkeypatch.setenv("PGPU_MERGED", merged)
-    rng = random.Random(77 + int(merged))
+    rng = random.Random(77 + case_set)
 
     def genome(kind, n):
         if kind == "random":

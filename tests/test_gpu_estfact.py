@@ -27,14 +27,17 @@ def exe():
                                  {"PINTRON_LANES": "1"}, {"PINTRON_LANES": "4", "PINTRON_SERVICES": "2", "PINTRON_FIBERS": "8"},
                                  {"PINTRON_NO_PREFETCH": "1", "PINTRON_THREADS": "3"},
                                  {"PINTRON_GPU_MEG": "0"},
-                                 {"PGPU_MERGED": "1"}, {"PGPU_MERGED": "0"}, {"PGPU_MERGED": "0", "PGPU_FANOUT": "0"},
+                                 # no suffix-array LCF tables (what a genome beyond the limit gets): every LCF job by the
+                                 # DP kernels; one service thread; the DP plans' outputs start from a poison pattern
+                                 {"PGPU_LCF_SA_MAX_BASES": "1"}, {"PINTRON_SERVICES": "1"}, {"PGPU_POISON": "255"},
                                  {"PGPU_WAIT": "0"}, {"PINTRON_NO_FIBER_POOL": "1", "PINTRON_NO_FIBER_PREFETCH": "1"},
-                                 # round 4's short cuts switched off one by one: questions in their turn, one-path graphs
-                                 # through the lists, alignments always over the whole matrix, an N prefix by the matrix kernel
-                                 {"PINTRON_AHEAD": "0"}, {"PINTRON_CHAIN": "0"}, {"PGPU_ALIGN_BAND": "0"}, {"PGPU_LCF_SA_N": "0"},
+                                 # round 4's short cuts of the host scheduler switched off one by one: questions in their
+                                 # turn, one-path graphs through the lists; a spinning wait; one parse and write thread
+                                 {"PINTRON_AHEAD": "0"}, {"PINTRON_CHAIN": "0"}, {"PGPU_WAIT": "-1"},
+                                 {"PINTRON_PARSE_THREADS": "1", "PINTRON_WRITE_THREADS": "1"},
                                  {"PINTRON_KEEP": "0", "PINTRON_PRE_RAMP": "1:2:3"},
                                  # ... and the end-exon alignments that answer the trimmed exon's check too
-                                 {"PINTRON_ENDPOINT_CHECKS": "0"}, {"PINTRON_ENDPOINT_CHECKS": "0", "PGPU_MERGED": "1"}])
+                                 {"PINTRON_ENDPOINT_CHECKS": "0"}, {"PINTRON_ENDPOINT_CHECKS": "0", "PGPU_POISON": "165"}])
 def test_ambn_golden(exe, tmp_path, env):
     for f in ("genomic.txt", "ests.txt"):
         shutil.copy(os.path.join(GOLD, f), tmp_path)
@@ -45,13 +48,13 @@ def test_ambn_golden(exe, tmp_path, env):
         assert filecmp.cmp(os.path.join(tmp_path, f), os.path.join(GOLD, "expected-" + f), shallow=False), f
 
 
-@pytest.mark.parametrize("env", [{}, {"PGPU_MERGED": "1"}, {"PGPU_MERGED": "0"},
-                                 {"PINTRON_AHEAD": "0", "PINTRON_CHAIN": "0", "PGPU_ALIGN_BAND": "0", "PGPU_LCF_SA_N": "0"},
-                                 {"PINTRON_ENDPOINT_CHECKS": "0"}])
+@pytest.mark.parametrize("env", [{}, {"PGPU_LCF_SA_MAX_BASES": "1"}, {"PINTRON_SERVICES": "1"},
+                                 {"PINTRON_AHEAD": "0", "PINTRON_CHAIN": "0"}, {"PINTRON_ENDPOINT_CHECKS": "0"}])
 def test_c3_sample_vs_compiled_reference(exe, tmp_path, env):
     """2 000 C3-shaped ESTs (200 kb genomic, 3 % errors): byte-identical to the reference binary
-    (oracle/_ref/est-fact-core travels with the repository snapshot), in every launch mode of the library
-    (one batch launch + LCF; wave-per-job launch + sweeps; a launch per family)."""
+    (oracle/_ref/est-fact-core travels with the repository snapshot), also without the suffix-array LCF tables
+    (every LCF job by the DP kernels), with one service thread, and with the host scheduler's short cuts switched
+    off (questions in their turn, one-path graphs through the lists; no end-exon checks)."""
     ref = os.path.join(ROOT, "oracle", "_ref", "est-fact-core")
     if not os.path.exists(ref):
         pytest.skip("oracle/_ref/est-fact-core not present")

@@ -1,5 +1,4 @@
-"""GPU: repeated whole-program runs across the launch modes of the library, worker counts and the MEG stage
-on/off -- a bit-exact product must give the reference's files EVERY time.  tools/stress_parity.py does the
+"""GPU: repeated whole-program runs across service-thread counts, worker counts and the MEG stage on/off -- a bit-exact product must give the reference's files EVERY time.  tools/stress_parity.py does the
 work and, on a mismatch, keeps what is needed to bisect it under gpurun_out/stress_test/ (both sides' files,
 a diff, the environment, PINTRON_VERBOSE output, and the verdict of replaying the run's DP requests through
 the oracle).  Round 2 saw one unexplained mismatch of the long-transcript input in eleven suite runs; this

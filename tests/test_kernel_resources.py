@@ -52,6 +52,5 @@ def test_dp_kernels_have_no_stack_frame(tmp_path):
         assert u.get("VGPRs Spill", 0) == 0, (name, u)
     batch = [u for k, u in kernels.items() if "dp_batch_kernel" in k][0]
     assert batch["VGPRs"] <= 128 and batch["Occupancy"] >= 4, batch
-    wave = [u for k, u in kernels.items() if "wave_jobs_kernel" in k][0]
-    # (dp_batch_kernel's LDS is dynamic: the same bytes + 256 static, see WAVE_JOBS_LDS's static_assert)
-    assert wave["LDS Size"] + 256 <= 40 * 1024, wave
+    # the dynamic LDS is bounded by WAVE_JOBS_LDS's static_assert, which allows for 256 B of static LDS
+    assert batch["LDS Size"] <= 256, batch

@@ -1,8 +1,10 @@
-"""GPU box: latency of one DP launch per family, row count and job count (event time of the group).
+"""GPU box: latency of a batch of one DP family, row count and job count (event time of each group).
 
 Usage: python tools/microbench_dp.py [reps]
-Prints one line per case: family, rows x columns, jobs, group name, microseconds (median of reps), and
-ns per sweep step (rows-on-lanes sweeps take about rows/R + columns steps)."""
+The groups of such a batch are `dp_batch` (the one launch of everything latency-bound) and the stand-alone
+long poles the library launches beside it (large row classes, strips, BORDERS beyond the batch's LDS, LCF).
+Prints one line per case and group: family, rows x columns, jobs, group name, microseconds (median of reps),
+and ns per sweep step (rows-on-lanes sweeps take about rows/R + columns steps)."""
 import os
 import random
 import statistics
@@ -64,7 +66,6 @@ def case(ctx, fam, la, lb, njobs, reps, rng):
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
     rng = random.Random(5)
-    os.environ.setdefault("PGPU_MERGED", "0")
     with capi.Context(0) as ctx:
         for fam, shapes in (
             ("AFFIX", [(23, 23), (60, 60), (96, 95), (200, 200), (400, 400), (900, 900)]),

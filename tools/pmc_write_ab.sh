@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: WRITE_SIZE of dp_batch_kernel over one 20 000-EST C3 step under a few settings (one --pmc pass each).
-#   bash tools/pmc_write_ab.sh "A=1" "PGPU_ALIGN_BAND=0" ...
+#   bash tools/pmc_write_ab.sh "A=1" "PINTRON_ENDPOINT_CHECKS=0" ...
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 for cfg in "$@"; do

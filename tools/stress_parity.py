@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Parity stress on the GPU box: the same inputs through pintron_amd/bin/est-fact many times, across the
-library's launch modes, worker counts and with the MEG stage on/off; every run's five files must have the
+"""Parity stress on the GPU box: the same inputs through pintron_amd/bin/est-fact many times, across
+service-thread counts (batches of several submitters overlapping on the GPU), worker counts and with the MEG
+stage on/off; every run's five files must have the
 checksums of the reference object code's run (oracle/_ref/est-fact-core).
 
 On a mismatch everything needed to bisect it is kept under --out: the differing files of both sides, a
@@ -27,8 +28,8 @@ EXE = os.environ.get("PINTRON_STRESS_EXE") or os.path.join(ROOT, "pintron_amd", 
 REF = os.path.join(ROOT, "oracle", "_ref", "est-fact-core")
 FILES = ["raw-multifasta-out.txt", "processed-ests.txt", "megs.txt", "processed-megs.txt", "meg-edges.txt"]
 
-MATRIX = [dict(PGPU_MERGED=m, PINTRON_THREADS=t, PINTRON_GPU_MEG=g)
-          for m, t, g in itertools.product(("2", "1", "0"), ("18", "2"), ("1", "0"))]
+MATRIX = [dict({"PINTRON_SERVICES": s} if s else {}, PINTRON_THREADS=t, PINTRON_GPU_MEG=g)     # services: default, 1, 2
+          for s, t, g in itertools.product((None, "1", "2"), ("18", "2"), ("1", "0"))]
 for _k, _e in enumerate(MATRIX):                 # every third setting without the end-exon alignments' exon checks
     if _k % 3 == 2:
         _e["PINTRON_ENDPOINT_CHECKS"] = "0"
