@@ -8,7 +8,6 @@
 #include <ctime>
 #include <time.h>
 #include <new>
-#include <string>
 #include <mutex>
 #include <vector>
 
@@ -295,30 +294,132 @@ extern "C" const char* pgpu_last_error(const pgpu_ctx* ctx) { return ctx ? ctx->
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-struct Group {
-  int family;            // KernelFamily
-  int kind;              // pgpu_dp_kind the jobs came from
-  int R;                 // row class (0 when not applicable)
-  size_t first, count;   // slice of the sorted device job table
-  uint32_t max_chunks = 0, max_l2 = 0;
-  uint32_t n_big = 0;          // leading jobs of the large row classes (ED, ALIGN, KBAND: above 16 rows per lane; GAP: above 4)
-  uint32_t max_rows = 0;       // largest a_len of the group (LDS of the one-job-per-workgroup BORDERS kernel)
-  bool launched = false;       // its events were recorded by the last launch
-  bool in_merged = false;      // its common row classes run inside the plan's batch launch; what is left here is the BIG part
-  uint64_t cells = 0, algo_bytes = 0;
-  uint64_t cells_big = 0, algo_big = 0;     // share of the first n_big jobs
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  float ms = 0.f;
-  float t0_ms = -1.f;          // start of the last launch on the device's time line (base_event), -1: unknown
-  std::string name;
-};
-
 uint32_t row_class(uint32_t rows) {         // smallest R in {1,2,4,...,64} with 64*R >= rows
   if (rows > 4096u) return ROW_CLASS_STRIPS;  // beyond that: strips of 4096 rows on the R = 64 kernels
   uint32_t R = 1;
   while (64u * R < rows) R <<= 1;
   return R;
 }
+
+// A route = the kernel that serves a job, as the statistics name it: a family, split by row class where different
+// kernels take the classes.  The device job table is sorted by family and row class (descending), so the jobs of
+// a route are one slice of it; the routes are listed in that order.
+enum DpRoute : uint8_t {
+  RT_ALIGN_STRIPS, RT_ALIGN_COOP, RT_ALIGN_WAVE, RT_GAP_SLOW, RT_GAP, RT_ED, RT_KBAND, RT_LCF,
+  RT_BORDERS_SLOW, RT_BORDERS_COOP, RT_BORDERS_WAVE, RT_AFFIX_STRIPS, RT_AFFIX_COOP, RT_AFFIX_WAVE,
+  RT_LCFSA, RT_LCFW, RT_ALIGNB,
+  RT_BATCH,              // the batch launch itself (no job is classified to it)
+  RT_COUNT
+};
+
+// place of a route's jobs in the batch launch
+enum BatchPlace { OUTSIDE, SEGMENT, ROLE_BORDERS, ROLE_AFFIX, ROLE_ALIGN };
+
+// traceback workspace of one job (la rows, lb columns, row class R) as the route's kernel lays it out
+using WsBytes = size_t (*)(uint32_t la, uint32_t lb, uint32_t R);
+size_t ws_align_wave(uint32_t, uint32_t lb, uint32_t) { return ((size_t)lb + 64) * 64; }               // [step][64 lanes], 1 B
+size_t ws_align_coop(uint32_t, uint32_t lb, uint32_t R) { return ((size_t)lb + 256) * 256 * align_coop_entry_bytes(R); }   // [step][256 lanes] (the band's words fit in there)
+size_t ws_align_strips(uint32_t la, uint32_t lb, uint32_t R) {      // two boundary rows, then the directions of every strip
+  return 2 * strip_bnd_bytes(lb) + (size_t)((la + 4095u) / 4096u) * ((size_t)lb + 64) * 64 * align_entry_bytes(R);
+}
+size_t ws_gap(uint32_t, uint32_t lb, uint32_t R) { return ((size_t)lb + 64) * 64 * gap_entry_bytes(R); }
+size_t ws_gap_slow(uint32_t la, uint32_t lb, uint32_t) { return (size_t)9 * ((size_t)la + 1) * 4 + ((size_t)la + 1) * ((size_t)lb + 1); }   // 9 rolling diagonals + 1 B per cell
+size_t ws_borders_slow(uint32_t la, uint32_t, uint32_t) { return (size_t)7 * ((size_t)la + 1) * 4; }   // 3 diagonals + 4 row-minima arrays
+size_t ws_affix_strips(uint32_t, uint32_t lb, uint32_t) { return 2 * strip_bnd_bytes(lb); }            // two boundary rows
+size_t ws_ed_strips(uint32_t la, uint32_t lb, uint32_t R) { return R == ROW_CLASS_STRIPS ? 2 * strip_bnd_bytes(std::max(la, lb)) : 0; }   // (ED, KBAND: the longer string is on the columns)
+
+// algorithmic HBM bytes of one job: operands once; 1 B/cell of directions for ALIGN, 3 B/cell
+// for GAP, read back, and two strings; 8 B per row when row minima are produced
+using AlgoBytes = uint64_t (*)(uint64_t la, uint64_t lb, uint64_t p2);
+uint64_t bytes_operands(uint64_t la, uint64_t lb, uint64_t) { return la + lb; }
+uint64_t bytes_align(uint64_t la, uint64_t lb, uint64_t) { return la + lb + la * lb + 3 * (la + lb); }
+uint64_t bytes_gap(uint64_t la, uint64_t lb, uint64_t) { return la + lb + 3 * la * lb + 3 * (la + lb); }
+// (BORDERS touches the first and the last t_win characters of t only)
+uint64_t bytes_borders(uint64_t la, uint64_t lb, uint64_t p2) { return la + std::min(lb, 2 * std::min(la + p2, lb)) + 2 * 8 * la; }
+// suffix-array search: s2, and per lane about eight table probes, a few suffix-array / sequence probes of the
+// bisection and the range minima, and the characters of one direct comparison
+uint64_t bytes_lcfsa(uint64_t, uint64_t lb, uint64_t) { return lb + 64u * 96u; }
+
+struct RouteInfo {
+  const char* name;        // in the statistics (bench.py maps these to kernel names)
+  int kind;                // pgpu_dp_kind it accounts to
+  int family;              // KernelFamily: sort key of the job table, body of a batch segment
+  WsBytes ws_bytes;        // nullptr: no workspace
+  bool strings;            // two alignment strings of la + lb + 1 bytes each
+  // cells = what the kernels compute (the roofline's numerator): this many per cell of the reference's loop bounds.
+  // The suffix-array search computes none of the 46 x |prefix| cells those bounds give: left out rather than credited
+  uint32_t cell_factor;
+  AlgoBytes algo_bytes;
+  BatchPlace place;
+  int seg_pos;             // SEGMENT: position among the batch launch's segments (long-running families first)
+  uint32_t big_from;       // SEGMENT: jobs of this row class and above keep a launch of their own (0: none do)
+  // what stays outside the batch launch: launch order (heaviest first; by_rows: + the longest pattern), auxiliary
+  // stream (-1: the main stream), launcher.  launch == nullptr: nothing of the route is ever left outside
+  long weight; bool by_rows; int lane; DpLauncher launch;
+  bool keyed;              // LCF: the kernel leaves one 64-bit key per job; at most 65535 jobs per launch (grid.y)
+};
+
+// Streams: HIP spreads its streams over four hardware queues, and what shares a queue runs one after the other:
+// four lanes (one per queue), the routes dealt out so that the four sums of typical durations come out even.
+constexpr RouteInfo ROUTES[] = {
+  // name                      kind             family     workspace        strs cells bytes           place        seg big  weight rows lane launcher            keyed
+  {"lev_wave<ALIGN,strips>",  PGPU_DP_ALIGN,   KF_ALIGN,   ws_align_strips, true,  1, bytes_align,    OUTSIDE,      0,  0,  5000, false,  2, launch_align_big,    false},
+  {"align_coop",              PGPU_DP_ALIGN,   KF_ALIGN,   ws_align_coop,   true,  1, bytes_align,    ROLE_ALIGN,   0,  0,     0, false,  0, nullptr,             false},
+  {"lev_wave<ALIGN>",         PGPU_DP_ALIGN,   KF_ALIGN,   ws_align_wave,   true,  1, bytes_align,    SEGMENT,      1,  0,     0, false,  0, nullptr,             false},
+  {"gap_slow",                PGPU_DP_GAP,     KF_GAP,     ws_gap_slow,     true,  3, bytes_gap,      OUTSIDE,      0,  0,  4000, false,  3, launch_gap_slow,     false},
+  {"gap_wave",                PGPU_DP_GAP,     KF_GAP,     ws_gap,          true,  3, bytes_gap,      SEGMENT,      2,  8,  4000, false,  3, launch_gap_big,      false},
+  {"lev_wave<ED>",            PGPU_DP_ED,      KF_ED,      ws_ed_strips,    false, 1, bytes_operands, SEGMENT,      8, 32,  1000, false,  1, launch_ed_big,       false},
+  {"lev_wave<KBAND>",         PGPU_DP_KBAND,   KF_KBAND,   ws_ed_strips,    false, 1, bytes_operands, SEGMENT,      3, 32,  2000, false,  2, launch_kband_big,    false},
+  {"lcf",                     PGPU_DP_LCF,     KF_LCF,     nullptr,         false, 1, bytes_operands, OUTSIDE,      0,  0,  3000, false,  3, launch_lcf,          true},
+  {"borders_slow",            PGPU_DP_BORDERS, KF_BORDERS, ws_borders_slow, false, 2, bytes_borders,  OUTSIDE,      0,  0, 10000, true,   1, launch_borders_slow, false},
+  {"borders_coop",            PGPU_DP_BORDERS, KF_BORDERS, nullptr,         false, 2, bytes_borders,  ROLE_BORDERS, 0,  0, 10000, true,   1, launch_borders_coop, false},   // outside when its row minima exceed the batch's LDS
+  {"lev_wave<BORDERS,R=1>",   PGPU_DP_BORDERS, KF_BORDERS, nullptr,         false, 2, bytes_borders,  SEGMENT,      4,  0,     0, false,  0, nullptr,             false},
+  {"lev_wave<AFFIX,strips>",  PGPU_DP_AFFIX,   KF_AFFIX,   ws_affix_strips, false, 1, bytes_operands, OUTSIDE,      0,  0, 10000, true,   0, launch_affix_strips, false},
+  {"affix_coop",              PGPU_DP_AFFIX,   KF_AFFIX,   nullptr,         false, 1, bytes_operands, ROLE_AFFIX,   0,  0,     0, false,  0, nullptr,             false},
+  {"lev_wave<AFFIX,R=1>",     PGPU_DP_AFFIX,   KF_AFFIX,   nullptr,         false, 1, bytes_operands, SEGMENT,      5,  0,     0, false,  0, nullptr,             false},
+  {"lcf_sa",                  PGPU_DP_LCF,     KF_LCFSA,   nullptr,         false, 0, bytes_lcfsa,    SEGMENT,      6,  0,     0, false,  0, nullptr,             false},
+  {"lcf_small",               PGPU_DP_LCF,     KF_LCFW,    nullptr,         false, 1, bytes_operands, SEGMENT,      7,  0,     0, false,  0, nullptr,             false},
+  {"align_band",              PGPU_DP_ALIGN,   KF_ALIGNB,  ws_align_coop,   true,  1, bytes_align,    SEGMENT,      0,  0,     0, false,  0, nullptr,             false},
+  // the batch launch: first of all, on the main stream, where the upload already is
+  {"dp_batch",                PGPU_DP_ALIGN,   KF_COUNT,   nullptr,         false, 0, nullptr,        OUTSIDE,      0,  0, 20000, false, -1, nullptr,             false},
+};
+static_assert(sizeof ROUTES / sizeof ROUTES[0] == RT_COUNT, "one entry per route, in the enum's order");
+constexpr bool routes_consistent() {
+  unsigned seen = 0;
+  for (const RouteInfo& ri : ROUTES) {
+    if (ri.lane >= pgpu_ctx::NAUX) return false;
+    if (ri.big_from && (ri.place != SEGMENT || !ri.launch)) return false;      // a big part is what a segment leaves outside
+    if (ri.place != SEGMENT) continue;
+    if (ri.seg_pos >= MAX_WAVE_SEGS || (seen & (1u << ri.seg_pos))) return false;   // one segment each
+    seen |= 1u << ri.seg_pos;
+  }
+  return true;
+}
+static_assert(routes_consistent(), "routing table");
+
+// a slice of the sorted device job table with its share of the accounting
+struct Slice { size_t first = 0, count = 0; uint64_t cells = 0, algo_bytes = 0; };
+
+// one entry of the statistics = one route's jobs of a plan (LCF: at most 65535 of them), or the batch launch
+struct Group {
+  DpRoute route;
+  Slice own;                   // what has a launch of its own; count 0: everything of the route runs in the batch launch
+  uint32_t max_chunks = 0, max_l2 = 0;    // LCF: most 256-diagonal chunks, longest s2
+  uint32_t max_rows = 0;       // largest a_len of the route's jobs (LDS of the one-job-per-workgroup BORDERS kernel)
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  float ms = 0.f;
+  float t0_ms = -1.f;          // start of the last launch on the device's time line (base_event), -1: unknown
+};
+
+// the batch launch of a plan
+struct BatchPlan {
+  BatchDesc desc;
+  uint32_t bc_max_rows;        // longest pattern of its BORDERS role
+  int ab_start, ab_count;      // its banded ALIGN jobs (the follow-up launch looks at them)
+};
+
+// a job between classification and the upload image; operands are addressed by OFFSET until the arena's place is known
+struct Keyed { DevJob j; uint64_t a_off, b_off; bool ag, bg; DpRoute route; uint32_t R; uint64_t size; };
 
 }  // namespace
 
@@ -345,13 +446,7 @@ struct pgpu_dp_plan {
   uint8_t* d_base = nullptr;
   uint8_t* h_up = nullptr; uint8_t* h_down = nullptr;
   size_t up_bytes = 0, off_results = 0, down_bytes = 0;
-  // batch launch (dp_batch_kernel): segments = the common row classes of the wave-per-job families ...
-  int n_segs = 0, seg_family[MAX_WAVE_SEGS] = {0}, seg_start[MAX_WAVE_SEGS] = {0}, seg_count[MAX_WAVE_SEGS] = {0};
-  LcfIndexView lcf_ix{};       // the index view the suffix-array LCF jobs search (one index per plan)
-  // ... and the one-job-per-workgroup BORDERS / AFFIX / ALIGN jobs
-  int bc_start = 0, bc_count = 0, ac_start = 0, ac_count = 0, lc_start = 0, lc_count = 0;   // BORDERS / AFFIX / ALIGN on several waves
-  int ab_start = 0, ab_count = 0;              // banded ALIGN jobs of the batch launch (the follow-up launch looks at them)
-  uint32_t bc_max_rows = 0;
+  BatchPlan batch{};           // (batch.desc.ix: the index view the suffix-array LCF jobs search, one index per plan)
   // LCF: the kernel leaves one 64-bit key per job directly in front of the results; they come back in the
   // same copy and sync turns them into results (lcf_out[k] = caller index of the job of key k)
   std::vector<uint32_t> lcf_out;
@@ -381,299 +476,240 @@ extern "C" int pgpu_dp_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const p
   return pgpu_dp_plan_create_parts(ctx, idx, &one, 1, out);
 }
 
-extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, const pgpu_dp_part* parts,
-                                         size_t n_parts, pgpu_dp_plan** out) {
-  if (!ctx || !out || (n_parts && !parts)) return set_err(ctx, PGPU_EINVAL, "bad argument");
-  *out = nullptr;
-  size_t n_jobs = 0, arena_len = 0;
-  for (size_t q = 0; q < n_parts; ++q) {
-    if ((parts[q].n_jobs && !parts[q].jobs) || (parts[q].arena_len && !parts[q].arena)) return set_err(ctx, PGPU_EINVAL, "bad argument");
-    n_jobs += parts[q].n_jobs; arena_len += parts[q].arena_len;
+// Route, row class and size of a job whose operands lie inside their spaces (k.j holds the caller's values).
+// `arena`: the caller's (LCF looks at the characters of s2).  Not PGPU_OK: the status the job gets without reaching the device
+static int classify(const pgpu_dp_job& in, const char* arena, bool ag, bool bg, const LcfIndexView& lcf, Keyed& k) {
+  const uint32_t la = in.a_len, lb = in.b_len;
+  k.size = (uint64_t)la * lb;
+  switch (in.kind) {
+    case PGPU_DP_ALIGN:
+      if (la > PGPU_MAX_ROWS_LEV || lb > PGPU_MAX_COLS) return PGPU_ERANGE;
+      k.R = row_class(la);
+      // exon against its stretch of the genomic sequence: the alignment hugs the diagonal.  Above 64 rows, lengths
+      // within the band's half-width: inside the band on ONE wave among the wave-per-job jobs (four to a workgroup
+      // instead of a workgroup each); the rare job the band cannot settle is finished by the follow-up launch
+      if (la > 64u && la <= 4096u && (la > lb ? la - lb : lb - la) <= ALIGN_BAND_HALF) k.route = RT_ALIGNB;
+      else k.route = k.R == 1 ? RT_ALIGN_WAVE : (k.R == ROW_CLASS_STRIPS ? RT_ALIGN_STRIPS : RT_ALIGN_COOP);
+      return PGPU_OK;
+    case PGPU_DP_GAP:
+      if (lb > PGPU_MAX_GAP_SIDE || la > PGPU_MAX_GAP_SIDE || ((uint64_t)la + 1) * ((uint64_t)lb + 1) > PGPU_MAX_GAP_CELLS) return PGPU_ERANGE;
+      // beyond 2048 rows: the anti-diagonal kernel over HBM (slow, but the reference computes these too)
+      k.R = la > PGPU_MAX_ROWS_GAP ? ROW_CLASS_STRIPS : row_class(la);
+      k.route = k.R == ROW_CLASS_STRIPS ? RT_GAP_SLOW : RT_GAP;
+      return PGPU_OK;
+    case PGPU_DP_ED:
+      if (std::min(la, lb) > PGPU_MAX_ROWS_LEV || std::max(la, lb) > PGPU_MAX_COLS) return PGPU_ERANGE;
+      k.R = row_class(std::min(la, lb)); k.route = RT_ED;
+      return PGPU_OK;
+    case PGPU_DP_KBAND: {
+      const uint32_t n = std::max(la, lb), m = std::min(la, lb), ub = in.p0;
+      if (n > PGPU_MAX_COLS || m > PGPU_MAX_ROWS_LEV) return PGPU_ERANGE;
+      k.R = row_class(m); k.route = RT_KBAND;
+      if (2ull * ub + 1 < n) k.size = (uint64_t)m * (2ull * ub + 1);
+      return PGPU_OK;
+    }
+    case PGPU_DP_LCF:
+      if (lb > 65535u || la >= (1u << 28)) return PGPU_ERANGE;
+      k.R = 0; k.route = RT_LCF;
+      // the small-exon search's question -- a prefix of the genomic sequence against a few dozen EST
+      // characters -- is answered from the suffix array when exact matching is all there is to it: both
+      // strings upper-case ACGT (no N wildcard can fire) and s2 short enough for one lane per start
+      // ... or with ONE N in s2 (an EST with a stray N): the four strings with A, C, G, T in its place are searched
+      // by the same wave (lcfsa_wave_body; job.p0 = the N's place + 1).  More Ns, or anything else: the DP kernel
+      if (lcf.focc && lcf.rmq && ag && !bg && in.a_off == 0 && la <= lcf.first_bad && lb <= 64u) {
+        const unsigned char* b = (const unsigned char*)arena + in.b_off;
+        bool acgt = true;
+        uint32_t n_wild = 0, wild_at = 0;
+        for (uint32_t q = 0; q < lb && acgt; ++q) {
+          if (b[q] == 'N' || b[q] == 'n') { ++n_wild; wild_at = q; }
+          else acgt = b[q] == 'A' || b[q] == 'C' || b[q] == 'G' || b[q] == 'T';
+        }
+        if (acgt && n_wild <= 1u) { k.route = RT_LCFSA; k.j.p0 = n_wild ? wild_at + 1u : 0u; }
+      }
+      // two short strings: one wave (a lane per diagonal) instead of a workgroup and an atomic per job
+      if (k.route == RT_LCF && (uint64_t)la * lb <= 16384u && la + lb <= 4096u) k.route = RT_LCFW;
+      return PGPU_OK;
+    case PGPU_DP_BORDERS: {
+      // only the first and the last t_win = min(len_p + max_errs, len_t) characters of t are swept
+      // (src/refine.c:117-121): t may be a whole intron of any length the index can hold
+      const uint64_t t_win = std::min<uint64_t>((uint64_t)la + in.p2, lb);
+      if (la > PGPU_MAX_ROWS_LEV || t_win > PGPU_MAX_COLS) return PGPU_ERANGE;
+      if (in.p0 > in.p1 || in.p1 > la) return PGPU_EINVAL;
+      // cells as the reference bounds them: two matrices of len_p x t_win; the gap of check_gap_errors is a whole
+      // intron, the window a few dozen columns
+      k.R = row_class(la); k.size = (uint64_t)la * t_win;
+      k.route = k.R == 1 ? RT_BORDERS_WAVE : (k.R == ROW_CLASS_STRIPS ? RT_BORDERS_SLOW : RT_BORDERS_COOP);
+      return PGPU_OK;
+    }
+    case PGPU_DP_AFFIX:
+      if (la > PGPU_MAX_ROWS_LEV || lb > PGPU_MAX_COLS) return PGPU_ERANGE;
+      k.R = row_class(la);
+      k.route = k.R == 1 ? RT_AFFIX_WAVE : (k.R == ROW_CLASS_STRIPS ? RT_AFFIX_STRIPS : RT_AFFIX_COOP);
+      return PGPU_OK;
+    default: return PGPU_EINVAL;
   }
-  if (n_jobs >= (size_t)1 << 30) return set_err(ctx, PGPU_EINVAL, "too many jobs");   // (the batch launch counts them in int)
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  pgpu_dp_plan* p = new (std::nothrow) pgpu_dp_plan();
-  if (!p) return set_err(ctx, PGPU_ENOMEM, "out of host memory");
-  p->n_jobs = n_jobs;
-  p->prefill.assign(n_jobs, pgpu_dp_result{});
+}
 
-  const uint8_t* d_gen = idx ? pgpu_index_genomic(idx) : nullptr;
-  const size_t gen_len = idx ? pgpu_index_length(idx) : 0;
-  p->lcf_ix = pgpu_index_lcf_view(idx);
-  const bool lcf_sa = idx && p->lcf_ix.focc && p->lcf_ix.rmq;
-  p->owner = ctx;
-  p->pooled = pgpu_ctx_pool_acquire(ctx, 0);
-
-  // pass 1: validate, classify; operands are addressed by OFFSET until the arena's place is known
-  struct Keyed { DevJob j; uint64_t a_off, b_off; bool ag, bg; int family; int kind; uint32_t R; uint64_t size; };
+// pass 1: validate and classify every job of every part; prefill[i] = the status of caller job i (PGPU_OK: it is in
+// the returned table).  Jobs of part q address part q's arena; the arenas are laid out one after the other.
+static std::vector<Keyed> classify_jobs(const pgpu_dp_part* parts, size_t n_parts, size_t n_jobs, const LcfIndexView& lcf,
+                                        bool has_genomic, size_t gen_len, std::vector<pgpu_dp_result>& prefill) {
   std::vector<Keyed> v;
   v.reserve(n_jobs);
-  // jobs of part q address part q's arena; the arenas are laid out one after the other
-  size_t i = 0, part_base = 0, part_i = 0, part_left = n_parts ? parts[0].n_jobs : 0;
-  for (; i < n_jobs; ++i, --part_left) {
-    while (part_left == 0) { part_base += parts[part_i].arena_len; ++part_i; part_left = parts[part_i].n_jobs; }
-    const pgpu_dp_job& in = parts[part_i].jobs[parts[part_i].n_jobs - part_left];
-    const size_t own_arena = parts[part_i].arena_len;
-    pgpu_dp_result& pre = p->prefill[i];
-    pre.status = PGPU_EINVAL;
-    if (in.kind >= PGPU_DP_NKINDS) continue;
-    const bool ag = in.flags & PGPU_JOB_A_GENOMIC, bg = in.flags & PGPU_JOB_B_GENOMIC;
-    if ((ag || bg) && !d_gen) continue;
-    const size_t a_space = ag ? gen_len : own_arena, b_space = bg ? gen_len : own_arena;
-    if (in.a_off > a_space || in.a_len > a_space - in.a_off) continue;
-    if (in.b_off > b_space || in.b_len > b_space - in.b_off) continue;
-    Keyed k{};
-    k.a_off = in.a_off + (ag ? 0 : part_base); k.b_off = in.b_off + (bg ? 0 : part_base); k.ag = ag; k.bg = bg;
-    k.j.la = in.a_len; k.j.lb = in.b_len;
-    k.j.p0 = in.p0; k.j.p1 = in.p1; k.j.p2 = in.p2; k.j.tail = in.tail;
-    k.j.out_idx = (uint32_t)i;
-    k.kind = (int)in.kind;
-    pre.status = PGPU_ERANGE;
-    const uint32_t la = in.a_len, lb = in.b_len;
-    switch (in.kind) {
-      case PGPU_DP_ALIGN:
-        if (la > PGPU_MAX_ROWS_LEV || lb > PGPU_MAX_COLS) continue;
-        k.family = KF_ALIGN; k.R = row_class(la); k.size = (uint64_t)la * lb;
-        // exon against its stretch of the genomic sequence: the alignment hugs the diagonal.  Above 64 rows, lengths
-        // within the band's half-width: inside the band on ONE wave among the wave-per-job jobs (four to a workgroup
-        // instead of a workgroup each); the rare job the band cannot settle is finished by the follow-up launch
-        if (la > 64u && la <= 4096u && (la > lb ? la - lb : lb - la) <= ALIGN_BAND_HALF)
-          k.family = KF_ALIGNB;
-        break;
-      case PGPU_DP_GAP:
-        if (lb > PGPU_MAX_GAP_SIDE || la > PGPU_MAX_GAP_SIDE || ((uint64_t)la + 1) * ((uint64_t)lb + 1) > PGPU_MAX_GAP_CELLS) continue;
-        // beyond 2048 rows: the anti-diagonal kernel over HBM (slow, but the reference computes these too)
-        k.family = KF_GAP; k.R = la > PGPU_MAX_ROWS_GAP ? ROW_CLASS_STRIPS : row_class(la); k.size = (uint64_t)la * lb; break;
-      case PGPU_DP_ED:
-        if (std::min(la, lb) > PGPU_MAX_ROWS_LEV || std::max(la, lb) > PGPU_MAX_COLS) continue;
-        k.family = KF_ED; k.R = row_class(std::min(la, lb)); k.size = (uint64_t)la * lb; break;
-      case PGPU_DP_KBAND: {
-        const uint32_t n = std::max(la, lb), m = std::min(la, lb), ub = in.p0;
-        if (n > PGPU_MAX_COLS || m > PGPU_MAX_ROWS_LEV) continue;
-        k.family = KF_KBAND; k.R = row_class(m);
-        k.size = (2ull * ub + 1 >= n) ? (uint64_t)la * lb : (uint64_t)m * (2ull * ub + 1);
-        break;
-      }
-      case PGPU_DP_LCF: {
-        if (lb > 65535u || la >= (1u << 28)) continue;
-        k.family = KF_LCF; k.R = 0; k.size = (uint64_t)la * lb;
-        // the small-exon search's question -- a prefix of the genomic sequence against a few dozen EST
-        // characters -- is answered from the suffix array when exact matching is all there is to it: both
-        // strings upper-case ACGT (no N wildcard can fire) and s2 short enough for one lane per start
-        // ... or with ONE N in s2 (an EST with a stray N): the four strings with A, C, G, T in its place are searched
-        // by the same wave (lcfsa_wave_body; job.p0 = the N's place + 1).  More Ns, or anything else: the DP kernel
-        if (lcf_sa && ag && !bg && in.a_off == 0 && la <= p->lcf_ix.first_bad && lb <= 64u) {
-          const unsigned char* b = (const unsigned char*)parts[part_i].arena + in.b_off;
-          bool acgt = true;
-          uint32_t n_wild = 0, wild_at = 0;
-          for (uint32_t q = 0; q < lb && acgt; ++q) {
-            if (b[q] == 'N' || b[q] == 'n') { ++n_wild; wild_at = q; }
-            else acgt = b[q] == 'A' || b[q] == 'C' || b[q] == 'G' || b[q] == 'T';
-          }
-          if (acgt && n_wild <= 1u) { k.family = KF_LCFSA; k.j.p0 = n_wild ? wild_at + 1u : 0u; }
-        }
-        // two short strings: one wave (a lane per diagonal) instead of a workgroup and an atomic per job
-        if (k.family == KF_LCF && (uint64_t)la * lb <= 16384u && la + lb <= 4096u) k.family = KF_LCFW;
-        break;
-      }
-      case PGPU_DP_BORDERS:
-        // only the first and the last t_win = min(len_p + max_errs, len_t) characters of t are swept
-        // (src/refine.c:117-121): t may be a whole intron of any length the index can hold
-        if (la > PGPU_MAX_ROWS_LEV || std::min<uint64_t>((uint64_t)la + in.p2, lb) > PGPU_MAX_COLS) continue;
-        if (in.p0 > in.p1 || in.p1 > la) { pre.status = PGPU_EINVAL; continue; }
-        // cells as the reference bounds them: two matrices of len_p x t_win, t_win = min(len_p + max_errs, len_t)
-        // (src/refine.c:117-121); the gap of check_gap_errors is a whole intron, the window a few dozen columns
-        k.family = KF_BORDERS; k.R = row_class(la); k.size = (uint64_t)la * std::min<uint64_t>((uint64_t)la + in.p2, lb); break;
-      case PGPU_DP_AFFIX:
-        if (la > PGPU_MAX_ROWS_LEV || lb > PGPU_MAX_COLS) continue;
-        k.family = KF_AFFIX; k.R = row_class(la); k.size = (uint64_t)la * lb; break;
-      default: continue;
+  prefill.assign(n_jobs, pgpu_dp_result{});
+  size_t i = 0, part_base = 0;
+  for (size_t q = 0; q < n_parts; part_base += parts[q].arena_len, ++q)
+    for (size_t w = 0; w < parts[q].n_jobs; ++w, ++i) {
+      const pgpu_dp_job& in = parts[q].jobs[w];
+      const size_t own_arena = parts[q].arena_len;
+      prefill[i].status = PGPU_EINVAL;
+      if (in.kind >= PGPU_DP_NKINDS) continue;
+      const bool ag = in.flags & PGPU_JOB_A_GENOMIC, bg = in.flags & PGPU_JOB_B_GENOMIC;
+      if ((ag || bg) && !has_genomic) continue;
+      const size_t a_space = ag ? gen_len : own_arena, b_space = bg ? gen_len : own_arena;
+      if (in.a_off > a_space || in.a_len > a_space - in.a_off) continue;
+      if (in.b_off > b_space || in.b_len > b_space - in.b_off) continue;
+      Keyed k{};
+      k.a_off = in.a_off + (ag ? 0 : part_base); k.b_off = in.b_off + (bg ? 0 : part_base); k.ag = ag; k.bg = bg;
+      k.j.la = in.a_len; k.j.lb = in.b_len;
+      k.j.p0 = in.p0; k.j.p1 = in.p1; k.j.p2 = in.p2; k.j.tail = in.tail;
+      k.j.out_idx = (uint32_t)i;
+      prefill[i].status = classify(in, parts[q].arena, ag, bg, lcf, k);
+      if (prefill[i].status != PGPU_OK) continue;
+      k.j.r_class = k.R;
+      v.push_back(k);
     }
-    k.j.r_class = k.R;
-    pre.status = PGPU_OK;
-    v.push_back(k);
-  }
-  // order: family, row class, then largest first (long jobs start early; waves of a workgroup
-  // and threads of a traceback wave get similar sizes)
-  // A counting sort does it in three passes: 13-bit key = family, row class (descending) and the
-  // size reduced to its binary order of magnitude (descending); jobs with the same key keep the
-  // caller's order.
-  {
-    auto key_of = [](const Keyed& k) -> uint32_t {
-      uint32_t rcls = 0;
-      while ((1u << rcls) < k.R) ++rcls;                                  // R = 0,1,2,4,...,128 -> 0..7
-      const uint32_t mag = 63u - (uint32_t)__builtin_clzll(k.size | 1ull);  // floor(log2(size)), 0..63
-      return ((uint32_t)k.family << 10) | ((7u - rcls) << 6) | (63u - mag);   // long jobs first
-    };
-    constexpr uint32_t NKEYS = (uint32_t)KF_COUNT << 10;
-    std::vector<uint32_t> start(NKEYS + 1, 0);
-    std::vector<uint32_t> kk(v.size());
-    for (size_t q = 0; q < v.size(); ++q) { kk[q] = key_of(v[q]); ++start[kk[q] + 1]; }
-    for (uint32_t c = 0; c < NKEYS; ++c) start[c + 1] += start[c];
-    std::vector<Keyed> sorted;
-    sorted.resize(v.size());
-    for (size_t q = 0; q < v.size(); ++q) sorted[start[kk[q]]++] = v[q];
-    v.swap(sorted);
-  }
-  // workspaces and string slots
-  size_t ws = 0, strs = 0, nkeys = 0;
-  for (auto& k : v) {
-    const uint32_t la = k.j.la, lb = k.j.lb;
-    if (k.R == ROW_CLASS_STRIPS && k.family == KF_GAP) {          // gap_slow_kernel: 9 rolling diagonals + 1 B per cell
-      k.j.ws_off = ws; ws += (size_t)9 * ((size_t)la + 1) * 4 + ((size_t)la + 1) * ((size_t)lb + 1);
-      k.j.str_off = strs; strs += 2 * ((size_t)la + lb + 1);
-    } else if (k.R == ROW_CLASS_STRIPS && k.family == KF_BORDERS) {   // borders_slow_kernel: 3 diagonals + 4 row-minima arrays
-      k.j.ws_off = ws; ws += (size_t)7 * ((size_t)la + 1) * 4;
-    } else if (k.R == ROW_CLASS_STRIPS) {     // two boundary rows, then (ALIGN) the directions of every strip
-      const uint32_t nc = (k.family == KF_ED || k.family == KF_KBAND) ? std::max(la, lb) : lb;
-      k.j.ws_off = ws; ws += 2 * strip_bnd_bytes(nc);
-      if (k.family == KF_ALIGN) {
-        ws += (size_t)((la + 4095u) / 4096u) * ((size_t)lb + 64) * 64 * align_entry_bytes(k.R);
-        k.j.str_off = strs; strs += 2 * ((size_t)la + lb + 1);
-      }
-    } else if (k.family == KF_ALIGN || k.family == KF_ALIGNB) {   // up to 64 rows: one wave; above: four waves,
-      // [step][256 lanes] entries (the band's words fit in there)
-      k.j.ws_off = ws; ws += k.R == 1 ? ((size_t)lb + 64) * 64 : ((size_t)lb + 256) * 256 * align_coop_entry_bytes(k.R);
-      k.j.str_off = strs; strs += 2 * ((size_t)la + lb + 1);
-    } else if (k.family == KF_GAP) {
-      k.j.ws_off = ws; ws += ((size_t)lb + 64) * 64 * gap_entry_bytes(k.R);
-      k.j.str_off = strs; strs += 2 * ((size_t)la + lb + 1);
-    } else if (k.family == KF_LCF) {
-      ++nkeys;
-      p->lcf_out.push_back(k.j.out_idx);
-    }                                           // (KF_LCFSA: no workspace, the wave writes its result itself)
-    ws = (ws + 15) & ~(size_t)15;
-  }
-  p->ws_bytes = ws; p->strs_bytes = strs; p->n_keys = nkeys; p->n_dev_jobs = v.size();
+  return v;
+}
 
-  // launch groups
-  auto cells_of = [](const Keyed& k) -> uint64_t { return k.size; };
-  i = 0;
-  while (i < v.size()) {
-    size_t j = i;
-    // a launch group = a family; BORDERS, AFFIX and ALIGN split into (up to 64 rows: one wave per job),
-    // (more rows: one job per workgroup) and (beyond 4096 rows: strips), GAP into (up to 2048 rows) and (more)
-    auto variant = [](const Keyed& k) -> int {
-      if (k.family == KF_GAP) return k.R == ROW_CLASS_STRIPS ? (int)ROW_CLASS_STRIPS : 0;
-      if (k.family != KF_BORDERS && k.family != KF_AFFIX && k.family != KF_ALIGN) return 0;
-      return k.R == 1 ? 1 : (k.R == ROW_CLASS_STRIPS ? (int)ROW_CLASS_STRIPS : 0);
-    };
+// pass 2: the order of the device job table: family, row class, then largest first (long jobs start early; waves of
+// a workgroup and threads of a traceback wave get similar sizes).  A counting sort does it in three passes: 13-bit
+// key = family, row class (descending) and the size reduced to its binary order of magnitude (descending); jobs
+// with the same key keep the caller's order.
+static void sort_jobs(std::vector<Keyed>& v) {
+  auto key_of = [](const Keyed& k) -> uint32_t {
+    uint32_t rcls = 0;
+    while ((1u << rcls) < k.R) ++rcls;                                  // R = 0,1,2,4,...,128 -> 0..7
+    const uint32_t mag = 63u - (uint32_t)__builtin_clzll(k.size | 1ull);  // floor(log2(size)), 0..63
+    return ((uint32_t)ROUTES[k.route].family << 10) | ((7u - rcls) << 6) | (63u - mag);   // long jobs first
+  };
+  constexpr uint32_t NKEYS = (uint32_t)KF_COUNT << 10;
+  std::vector<uint32_t> start(NKEYS + 1, 0);
+  std::vector<uint32_t> kk(v.size());
+  for (size_t q = 0; q < v.size(); ++q) { kk[q] = key_of(v[q]); ++start[kk[q] + 1]; }
+  for (uint32_t c = 0; c < NKEYS; ++c) start[c + 1] += start[c];
+  std::vector<Keyed> sorted;
+  sorted.resize(v.size());
+  for (size_t q = 0; q < v.size(); ++q) sorted[start[kk[q]]++] = v[q];
+  v.swap(sorted);
+}
+
+// pass 3: workspaces, string slots and LCF keys (lcf_out[k] = caller index of the job of key k) in table order
+struct DpSpace { size_t ws = 0, strs = 0; };
+static DpSpace assign_workspace(std::vector<Keyed>& v, std::vector<uint32_t>& lcf_out) {
+  DpSpace sp;
+  for (auto& k : v) {
+    const RouteInfo& ri = ROUTES[k.route];
+    const size_t wb = ri.ws_bytes ? ri.ws_bytes(k.j.la, k.j.lb, k.R) : 0;
+    if (wb) { k.j.ws_off = sp.ws; sp.ws += wb; }
+    if (ri.strings) { k.j.str_off = sp.strs; sp.strs += 2 * ((size_t)k.j.la + k.j.lb + 1); }
+    if (ri.keyed) lcf_out.push_back(k.j.out_idx);
+    sp.ws = (sp.ws + 15) & ~(size_t)15;
+  }
+  return sp;
+}
+
+// pass 4: one group per route present (the jobs of a route are adjacent).  batched[g] = what of group g runs inside
+// the batch launch: of a SEGMENT route all but the leading jobs of the large row classes, of a role route everything
+// -- unless the largest BORDERS pattern needs more LDS than the roles may share.  cells / algo_bytes: per pgpu_dp_kind
+static void form_groups(const std::vector<Keyed>& v, std::vector<Group>& groups, std::vector<Slice>& batched,
+                        uint64_t* cells, uint64_t* algo_bytes) {
+  for (size_t i = 0, j; i < v.size(); i = j) {
+    const RouteInfo& ri = ROUTES[v[i].route];
     Group g{};
-    g.family = v[i].family; g.kind = v[i].kind; g.R = variant(v[i]); g.first = i;
-    while (j < v.size() && v[j].family == g.family && variant(v[j]) == g.R &&
-           (g.family != KF_LCF || j - i < 65535)) {
+    g.route = v[i].route;
+    Slice big, rest;
+    for (j = i; j < v.size() && v[j].route == g.route && !(ri.keyed && j - i == 65535); ++j) {
       const Keyed& k = v[j];
-      const uint64_t la = k.j.la, lb = k.j.lb;
-      // cells = what the kernels compute (the roofline's numerator).  The suffix-array search computes none of the
-      // 46 x |prefix| cells the reference's loop bounds give for these jobs: they are left out rather than credited
-      const uint64_t job_cells = k.family == KF_LCFSA ? 0 : (k.family == KF_GAP ? 3 : (k.family == KF_BORDERS ? 2 : 1)) * cells_of(k);
-      // algorithmic HBM bytes: operands once; 1 B/cell of directions for
-      // ALIGN, 3 B/cell for GAP; 8 B per row when row minima are produced
-      // (BORDERS touches the first and the last t_win characters of t only)
-      uint64_t job_bytes = la + (k.family == KF_BORDERS ? std::min<uint64_t>(lb, 2 * std::min<uint64_t>(la + k.j.p2, lb)) : lb);
-      if (k.family == KF_ALIGN || k.family == KF_ALIGNB) job_bytes += la * lb + 3 * (la + lb);     // + directions read back, two strings
-      if (k.family == KF_GAP) job_bytes += 3 * la * lb + 3 * (la + lb);
-      if (k.family == KF_BORDERS) job_bytes += 2 * 8 * la;
-      // suffix-array search: s2, and per lane about eight table probes, a few suffix-array / sequence probes of the
-      // bisection and the range minima, and the characters of one direct comparison
-      if (k.family == KF_LCFSA) job_bytes = lb + 64u * 96u;
-      g.cells += job_cells; g.algo_bytes += job_bytes;
-      g.max_rows = std::max(g.max_rows, (uint32_t)la);
-      if (k.family != KF_ALIGNB && k.R >= (k.family == KF_GAP ? 8u : 32u)) { ++g.n_big; g.cells_big += job_cells; g.algo_big += job_bytes; }   // (the slow GAP / BORDERS groups ignore it)
-      if (k.family == KF_LCF) {
-        const uint32_t ch = (uint32_t)((la + lb + 254) / 256);   // ceil((la+lb-1)/256) diagonals
-        g.max_chunks = std::max(g.max_chunks, ch);
-        g.max_l2 = std::max(g.max_l2, (uint32_t)lb);
+      Slice& s = ri.big_from && k.R >= ri.big_from ? big : rest;
+      ++s.count; s.cells += ri.cell_factor * k.size; s.algo_bytes += ri.algo_bytes(k.j.la, k.j.lb, k.j.p2);
+      g.max_rows = std::max(g.max_rows, k.j.la);
+      if (ri.keyed) {
+        g.max_chunks = std::max(g.max_chunks, (uint32_t)(((uint64_t)k.j.la + k.j.lb + 254) / 256));   // ceil((la+lb-1)/256) diagonals
+        g.max_l2 = std::max(g.max_l2, k.j.lb);
       }
-      ++j;
     }
-    g.count = j - i;
-    char nm[64];
-    static const char* fam[] = {"lev_wave<ALIGN>", "gap_wave", "lev_wave<ED>", "lev_wave<KBAND>", "lcf",
-                                "borders_coop", "affix_coop", "lcf_sa", "lcf_small", "align_band"};
-    if (g.family == KF_BORDERS && g.R == 1) snprintf(nm, sizeof nm, "lev_wave<BORDERS,R=1>");
-    else if (g.family == KF_AFFIX && g.R == 1) snprintf(nm, sizeof nm, "lev_wave<AFFIX,R=1>");
-    else if (g.family == KF_AFFIX && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "lev_wave<AFFIX,strips>");
-    else if (g.family == KF_BORDERS && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "borders_slow");
-    else if (g.family == KF_GAP && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "gap_slow");
-    else if (g.family == KF_ALIGN && g.R == 0) snprintf(nm, sizeof nm, "align_coop");
-    else if (g.family == KF_ALIGN && g.R == (int)ROW_CLASS_STRIPS) snprintf(nm, sizeof nm, "lev_wave<ALIGN,strips>");
-    else snprintf(nm, sizeof nm, "%s", fam[g.family]);
-    g.name = nm;
-    p->groups.push_back(g);
-    i = j;
+    big.first = i; rest.first = i + big.count;
+    cells[ri.kind] += big.cells + rest.cells; algo_bytes[ri.kind] += big.algo_bytes + rest.algo_bytes;
+    const bool in_batch = ri.place == ROLE_BORDERS ? dp_batch_lds_bytes(true, 1, g.max_rows, 1, 1) <= DP_BATCH_MAX_LDS : ri.place != OUTSIDE;
+    g.own = in_batch ? big : rest;      // (only SEGMENT routes have a big part, and they are always in the batch)
+    groups.push_back(g);
+    batched.push_back(in_batch ? rest : Slice{});
   }
-  for (auto& g : p->groups) {
-    p->cells[g.kind] += g.cells;
-    p->algo_bytes[g.kind] += g.algo_bytes;
-  }
-  {
-    // ONE launch (dp_batch_kernel) for the latency-bound part of the batch: the common row classes of the
-    // wave-per-job families, long-running families first (the groups keep their BIG part, the first n_big
-    // jobs), and the one-job-per-workgroup sweeps unless the largest BORDERS pattern needs more LDS than the
-    // roles may share
-    static constexpr int order_fam[9] = { KF_ALIGNB, KF_ALIGN, KF_GAP, KF_KBAND, KF_BORDERS, KF_AFFIX, KF_LCFSA, KF_LCFW, KF_ED };
-    static_assert(sizeof order_fam / sizeof order_fam[0] <= MAX_WAVE_SEGS, "one segment per family at most");
-    Group m{};
-    m.family = KF_COUNT; m.kind = PGPU_DP_ALIGN; m.name = "dp_batch";
-    for (int f : order_fam)
-      for (auto& g : p->groups) {
-        if (g.family != f) continue;
-        const bool split = f == KF_BORDERS || f == KF_AFFIX || f == KF_ALIGN;   // one wave up to 64 rows, several above
-        const bool wave_family = split ? g.R == 1 : g.R == 0;
-        if (!wave_family) continue;
-        const size_t big = split ? 0 : g.n_big;
-        if (g.count <= big) continue;
-        p->seg_family[p->n_segs] = f; p->seg_start[p->n_segs] = (int)(g.first + big); p->seg_count[p->n_segs] = (int)(g.count - big);
-        ++p->n_segs;
-        if (f == KF_ALIGNB) { p->ab_start = (int)g.first; p->ab_count = (int)g.count; }
-        m.count += g.count - big; m.cells += g.cells - (big ? g.cells_big : 0); m.algo_bytes += g.algo_bytes - (big ? g.algo_big : 0);
-        g.in_merged = true;
-        g.count = big; g.cells = big ? g.cells_big : 0; g.algo_bytes = big ? g.algo_big : 0;
-      }
-    bool coop = false;
-    for (auto& g : p->groups) {
-      if (g.R != 0 || g.count == 0) continue;
-      if (g.family == KF_BORDERS && dp_batch_lds_bytes(true, 1, g.max_rows, 1, 1) <= 64 * 1024) {
-        p->bc_start = (int)g.first; p->bc_count = (int)g.count; p->bc_max_rows = g.max_rows;
-      } else if (g.family == KF_AFFIX) {
-        p->ac_start = (int)g.first; p->ac_count = (int)g.count;
-      } else if (g.family == KF_ALIGN) {
-        p->lc_start = (int)g.first; p->lc_count = (int)g.count;
-      } else continue;
-      m.count += g.count; m.cells += g.cells; m.algo_bytes += g.algo_bytes;
-      g.in_merged = true; g.count = 0; g.cells = 0; g.algo_bytes = 0;
-      coop = true;
+}
+
+// pass 5: the batch launch from what the groups hand it; when there is one, its group is appended (the entry of the
+// statistics that carries its timing and accounting)
+static void form_batch(std::vector<Group>& groups, const std::vector<Slice>& batched, BatchPlan& b) {
+  Group m{};
+  m.route = RT_BATCH;
+  const Slice* seg[MAX_WAVE_SEGS] = {nullptr};
+  int seg_family[MAX_WAVE_SEGS] = {0};
+  BatchDesc& d = b.desc;
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    const Slice& s = batched[gi];
+    if (!s.count) continue;
+    const RouteInfo& ri = ROUTES[groups[gi].route];
+    switch (ri.place) {
+      case SEGMENT:      seg[ri.seg_pos] = &s; seg_family[ri.seg_pos] = ri.family; break;
+      case ROLE_BORDERS: d.bc_start = (int)s.first; d.bc_count = (int)s.count; b.bc_max_rows = groups[gi].max_rows; break;
+      case ROLE_AFFIX:   d.ac_start = (int)s.first; d.ac_count = (int)s.count; break;
+      case ROLE_ALIGN:   d.lc_start = (int)s.first; d.lc_count = (int)s.count; break;
+      case OUTSIDE:      break;
     }
-    if (p->n_segs || coop) p->groups.push_back(m);       // the pseudo group that carries its timing and accounting
+    if (groups[gi].route == RT_ALIGNB) { b.ab_start = (int)s.first; b.ab_count = (int)s.count; }
+    m.own.count += s.count; m.own.cells += s.cells; m.own.algo_bytes += s.algo_bytes;
   }
+  int waves = 0;
+  for (int q = 0; q < MAX_WAVE_SEGS; ++q) {
+    if (!seg[q]) continue;
+    d.segs.family[d.segs.n] = seg_family[q]; d.segs.start[d.segs.n] = (int)seg[q]->first; d.segs.count[d.segs.n] = (int)seg[q]->count;
+    ++d.segs.n;
+    waves += (int)seg[q]->count;
+  }
+  d.wave_blocks = (waves + 3) / 4;
+  if (m.own.count) groups.push_back(m);
+}
+
+// events of the groups (timing only), the one device allocation, the pinned images and the upload: the only part of
+// plan creation that touches the context and HIP.  On failure the caller frees the plan
+static int plan_upload(pgpu_ctx* ctx, pgpu_dp_plan* p, const pgpu_dp_part* parts, size_t n_parts, size_t arena_len,
+                       const std::vector<Keyed>& v, const uint8_t* d_gen) {
   if (ctx->timing) {
     const size_t need = 2 * p->groups.size();
     if (p->pooled) {
       while (ctx->ev_pool.size() < need) {
         hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) { plan_free(p); return set_err(ctx, PGPU_EDEVICE, "hipEventCreate failed"); }
+        if (hipEventCreate(&e) != hipSuccess) return set_err(ctx, PGPU_EDEVICE, "hipEventCreate failed");
         ctx->ev_pool.push_back(e);
       }
       for (size_t g = 0; g < p->groups.size(); ++g) { p->groups[g].ev0 = ctx->ev_pool[2 * g]; p->groups[g].ev1 = ctx->ev_pool[2 * g + 1]; }
     } else {
       for (auto& g : p->groups)
-        if (hipEventCreate(&g.ev0) != hipSuccess || hipEventCreate(&g.ev1) != hipSuccess) {
-          plan_free(p);
-          return set_err(ctx, PGPU_EDEVICE, "hipEventCreate failed");
-        }
+        if (hipEventCreate(&g.ev0) != hipSuccess || hipEventCreate(&g.ev1) != hipSuccess) return set_err(ctx, PGPU_EDEVICE, "hipEventCreate failed");
     }
   }
 
   // one device allocation, one pinned upload image, one pinned download image
   auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t n_jobs = p->n_jobs, strs = p->strs_bytes;
   const size_t off_arena = 0;
   const size_t off_jobs = up256(arena_len + 16);
   const size_t off_keys = up256(off_jobs + std::max<size_t>(v.size(), 1) * sizeof(DevJob));
-  const size_t off_results = up256(off_keys + (nkeys + 1) * sizeof(unsigned long long));
+  const size_t off_results = up256(off_keys + (p->n_keys + 1) * sizeof(unsigned long long));
   const size_t off_strs = off_results + std::max<size_t>(n_jobs, 1) * sizeof(DevResult);   // directly behind the results
   const size_t off_ws = up256(off_strs + strs + 16);
-  const size_t total = off_ws + ws + 16;
+  const size_t total = off_ws + p->ws_bytes + 16;
   p->up_bytes = off_strs;                      // arena .. results (prefilled)
   p->off_results = off_results;
   p->off_keys = off_keys;
@@ -688,10 +724,8 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
     if (hipHostMalloc(&q, p->up_bytes, hipHostMallocDefault) == hipSuccess) p->h_up = (uint8_t*)q;
     if (hipHostMalloc(&q, p->down_bytes + 16, hipHostMallocDefault) == hipSuccess) p->h_down = (uint8_t*)q;
   }
-  if (!p->d_base || !p->h_up || !p->h_down) {
-    plan_free(p);
+  if (!p->d_base || !p->h_up || !p->h_down)
     return set_err(ctx, PGPU_ENOMEM, "batch buffers (%zu B device, %zu B pinned) could not be allocated", total, p->up_bytes + p->down_bytes);
-  }
   p->d_arena = p->d_base + off_arena;
   p->d_jobs = (DevJob*)(p->d_base + off_jobs);
   p->d_keys = (unsigned long long*)(p->d_base + off_keys);
@@ -715,13 +749,44 @@ extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, c
   memset(p->h_up + off_keys, 0, off_results - off_keys);
   if (n_jobs) memcpy(p->h_up + off_results, p->prefill.data(), n_jobs * sizeof(DevResult));
   const hipError_t e = hipMemcpyAsync(p->d_base, p->h_up, p->up_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) { plan_free(p); return set_err(ctx, PGPU_EDEVICE, "upload failed: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) return set_err(ctx, PGPU_EDEVICE, "upload failed: %s", hipGetErrorString(e));
   if (ctx->poison >= 0) {
     // debugging aid (PGPU_POISON=<byte>): what the kernels are going to write -- strings, traceback workspace --
     // starts from a known pattern instead of whatever the previous batch left there; an answer that changes
     // with the pattern comes from a read of memory nothing wrote (tools/stress_parity.py --poison)
-    if (hipMemsetAsync(p->d_base + off_strs, ctx->poison, total - off_strs, ctx->stream) != hipSuccess) { plan_free(p); return set_err(ctx, PGPU_EDEVICE, "poison fill failed"); }
+    if (hipMemsetAsync(p->d_base + off_strs, ctx->poison, total - off_strs, ctx->stream) != hipSuccess) return set_err(ctx, PGPU_EDEVICE, "poison fill failed");
   }
+  return PGPU_OK;
+}
+
+extern "C" int pgpu_dp_plan_create_parts(pgpu_ctx* ctx, const pgpu_index* idx, const pgpu_dp_part* parts,
+                                         size_t n_parts, pgpu_dp_plan** out) {
+  if (!ctx || !out || (n_parts && !parts)) return set_err(ctx, PGPU_EINVAL, "bad argument");
+  *out = nullptr;
+  size_t n_jobs = 0, arena_len = 0;
+  for (size_t q = 0; q < n_parts; ++q) {
+    if ((parts[q].n_jobs && !parts[q].jobs) || (parts[q].arena_len && !parts[q].arena)) return set_err(ctx, PGPU_EINVAL, "bad argument");
+    n_jobs += parts[q].n_jobs; arena_len += parts[q].arena_len;
+  }
+  if (n_jobs >= (size_t)1 << 30) return set_err(ctx, PGPU_EINVAL, "too many jobs");   // (the batch launch counts them in int)
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  pgpu_dp_plan* p = new (std::nothrow) pgpu_dp_plan();
+  if (!p) return set_err(ctx, PGPU_ENOMEM, "out of host memory");
+  p->n_jobs = n_jobs;
+  p->owner = ctx;
+  p->pooled = pgpu_ctx_pool_acquire(ctx, 0);
+  p->batch.desc.ix = pgpu_index_lcf_view(idx);
+
+  std::vector<Keyed> v = classify_jobs(parts, n_parts, n_jobs, p->batch.desc.ix, idx != nullptr, idx ? pgpu_index_length(idx) : 0, p->prefill);
+  sort_jobs(v);
+  const DpSpace sp = assign_workspace(v, p->lcf_out);
+  p->ws_bytes = sp.ws; p->strs_bytes = sp.strs; p->n_keys = p->lcf_out.size(); p->n_dev_jobs = v.size();
+  std::vector<Slice> batched;
+  form_groups(v, p->groups, batched, p->cells, p->algo_bytes);
+  form_batch(p->groups, batched, p->batch);
+
+  const int rc = plan_upload(ctx, p, parts, n_parts, arena_len, v, idx ? pgpu_index_genomic(idx) : nullptr);
+  if (rc != PGPU_OK) { plan_free(p); return rc; }
   *out = p;
   return PGPU_OK;
 }
@@ -731,50 +796,26 @@ extern "C" int pgpu_dp_plan_launch(pgpu_ctx* ctx, pgpu_dp_plan* p) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   p->synced = false; p->lcf_decoded = false;       // a relaunch downloads anew: the image holds raw keys again
   // Launch order: the groups are independent, and the host needs a few microseconds per launch, so
-  // the long poles go first: the batch launch, the one-job-per-workgroup sweeps it does not hold, the
-  // large alignments, ... and the large edit distances last.
+  // the long poles go first (RouteInfo.weight): the batch launch, the one-job-per-workgroup sweeps it does not
+  // hold, the large alignments, ... and the large edit distances last.
   std::vector<size_t> order;
   std::vector<size_t> key_of(p->groups.size(), 0);
+  auto weight = [&](size_t gi) -> long {
+    const RouteInfo& ri = ROUTES[p->groups[gi].route];
+    return ri.weight + (ri.by_rows ? (long)p->groups[gi].max_rows : 0);
+  };
   {
     size_t kb = 0;
     for (size_t gi = 0; gi < p->groups.size(); ++gi) {
       const Group& g = p->groups[gi];
-      if (g.family == KF_LCF) { key_of[gi] = kb; kb += g.count; }
-      if (g.in_merged && g.count == 0) continue;           // nothing left outside the batch launch
-      order.push_back(gi);
+      if (ROUTES[g.route].keyed) { key_of[gi] = kb; kb += g.own.count; }
+      if (g.own.count) order.push_back(gi);                // (0: nothing left outside the batch launch)
     }
-    auto weight = [&](size_t gi) -> long {
-      const Group& g = p->groups[gi];
-      switch (g.family) {
-        case KF_COUNT: return 20000;
-        case KF_BORDERS: case KF_AFFIX: return 10000 + (long)g.max_rows;
-        case KF_ALIGN: return 5000;
-        case KF_GAP: return 4000;
-        case KF_LCF: return 3000;
-        case KF_KBAND: return 2000;
-        default: return 1000;
-      }
-    };
     std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weight(a) > weight(b); });
   }
-  // HIP spreads its streams over four hardware queues, and what shares a queue runs one after the
-  // other: four streams (one per queue), the families dealt out so that the four sums of typical
-  // durations come out even; the batch launch stays on the main stream (lane -1), where the upload
-  // already is, and only the streams a plan uses are forked and joined.
-  std::vector<int> lane_of(order.size(), 0);
+  // only the auxiliary streams (RouteInfo.lane) a plan uses are forked and joined
   unsigned used_mask = 0;
-  for (size_t oi = 0; oi < order.size(); ++oi) {
-    int l;
-    switch (p->groups[order[oi]].family) {
-      case KF_AFFIX:   l = 0; break;
-      case KF_BORDERS: case KF_ED: l = 1; break;
-      case KF_COUNT:   l = -1; break;
-      case KF_ALIGN: case KF_KBAND: l = 2; break;
-      default: l = 3; break;           // GAP, LCF
-    }
-    lane_of[oi] = l;
-    if (l >= 0) used_mask |= 1u << l;
-  }
+  for (size_t gi : order) { const int l = ROUTES[p->groups[gi].route].lane; if (l >= 0) used_mask |= 1u << l; }
   if (used_mask) {            // fork: the upload (plan_create) is on the main stream
     HIP_TRY(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));
     for (int i = 0; i < pgpu_ctx::NAUX; ++i)
@@ -783,37 +824,25 @@ extern "C" int pgpu_dp_plan_launch(pgpu_ctx* ctx, pgpu_dp_plan* p) {
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux[i], ctx->ev_upload, 0));
       }
   }
-  for (size_t oi = 0; oi < order.size(); ++oi) {
-    const size_t gi = order[oi];
+  for (size_t gi : order) {
     Group& g = p->groups[gi];
-    const DevJob* jobs = p->d_jobs + g.first;
-    const int n = (int)g.count;
-    hipStream_t st = lane_of[oi] >= 0 ? ctx->aux[lane_of[oi]] : ctx->stream;
+    const RouteInfo& ri = ROUTES[g.route];
+    hipStream_t st = ri.lane >= 0 ? ctx->aux[ri.lane] : ctx->stream;
     if (g.ev0) HIP_TRY(ctx, hipEventRecord(g.ev0, st));
-    g.launched = true;
-    pgpu_range_push(g.name.c_str());
+    pgpu_range_push(ri.name);
     struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
-    switch (g.family) {
-      case KF_COUNT:
-        if (!launch_dp_batch(p->d_jobs, p->n_segs, p->seg_family, p->seg_start, p->seg_count, p->bc_start, p->bc_count,
-                             p->bc_max_rows, p->ac_start, p->ac_count, p->lc_start, p->lc_count, p->d_results, p->d_ws, p->d_strs, p->lcf_ix, st))
-          return set_err(ctx, PGPU_EDEVICE, "batch launch: LDS budget exceeded");
-        break;
-      case KF_ALIGN: case KF_ED: case KF_BORDERS: case KF_AFFIX: case KF_KBAND:
-        launch_lev(g.family, g.R, g.max_rows, jobs, n, p->d_results, p->d_ws, p->d_strs, st); break;
-      case KF_GAP:
-        if (g.R == (int)ROW_CLASS_STRIPS) launch_gap_slow(jobs, n, p->d_results, p->d_ws, p->d_strs, st);
-        else launch_gap(jobs, n, p->d_results, p->d_ws, p->d_strs, st);
-        break;
-      case KF_LCF:
-        launch_lcf(jobs, n, g.max_chunks, g.max_l2, p->d_keys + key_of[gi], st);
-        break;
-      default: break;
+    if (g.route == RT_BATCH) {
+      if (!launch_dp_batch(p->d_jobs, p->batch.desc, p->batch.bc_max_rows, p->d_results, p->d_ws, p->d_strs, st))
+        return set_err(ctx, PGPU_EDEVICE, "batch launch: LDS budget exceeded");
+    } else {
+      if (!ri.launch) return set_err(ctx, PGPU_EDEVICE, "no kernel for %zu jobs of %s outside the batch launch", g.own.count, ri.name);
+      ri.launch(DpLaunch{p->d_jobs + g.own.first, (int)g.own.count, g.max_rows, g.max_chunks, g.max_l2, p->d_results, p->d_ws,
+                         p->d_strs, p->d_keys + key_of[gi], st});
     }
     if (g.ev1) HIP_TRY(ctx, hipEventRecord(g.ev1, st));
     // behind the batch launch (and outside its pair of events, which time the one kernel the profiler lists as
-    // dp_batch_kernel): the whole-matrix sweep of the banded alignments it could not settle
-    if (g.family == KF_COUNT) launch_align_fallback(p->d_jobs + p->ab_start, p->ab_count, p->d_results, p->d_ws, p->d_strs, st);
+    // dp_batch_kernel; ADVICE.md): the whole-matrix sweep of the banded alignments it could not settle
+    if (g.route == RT_BATCH) launch_align_fallback(p->d_jobs + p->batch.ab_start, p->batch.ab_count, p->d_results, p->d_ws, p->d_strs, st);
     HIP_TRY(ctx, hipGetLastError());
   }
   for (int i = 0; i < pgpu_ctx::NAUX; ++i) {      // join: the main stream continues after every stream that was used
@@ -853,11 +882,11 @@ extern "C" int pgpu_dp_plan_sync(pgpu_ctx* ctx, pgpu_dp_plan* p) {
     for (int k = 0; k < PGPU_DP_NKINDS; ++k) { p->ms[k] = 0; p->launches[k] = 0; }
     for (auto& g : p->groups) {
       float ms = 0.f;
-      if (!g.launched) continue;            // everything of this group ran inside the batch launch
+      if (!g.own.count) continue;           // everything of this group ran inside the batch launch
       if (g.ev0 && g.ev1 && hipEventElapsedTime(&ms, g.ev0, g.ev1) == hipSuccess) g.ms = ms;
       if (g.ev0) { hipEvent_t b = base_event(ctx->device, ctx->stream); float t0 = 0.f; g.t0_ms = (b && hipEventElapsedTime(&t0, b, g.ev0) == hipSuccess) ? t0 : -1.f; }
-      p->ms[g.kind] += g.ms;
-      p->launches[g.kind] += 1;
+      p->ms[ROUTES[g.route].kind] += g.ms;
+      p->launches[ROUTES[g.route].kind] += 1;
     }
   }
   return PGPU_OK;
@@ -922,8 +951,8 @@ extern "C" int pgpu_dp_plan_group_info(const pgpu_dp_plan* p, int i, pgpu_group_
   if (!p || !out || i < 0 || i >= (int)p->groups.size()) return PGPU_EINVAL;
   const Group& g = p->groups[i];
   memset(out, 0, sizeof(*out));
-  snprintf(out->name, sizeof(out->name), "%s", g.name.c_str());
-  out->kind = g.kind; out->jobs = g.count; out->cells = g.cells; out->algo_bytes = g.algo_bytes;
+  snprintf(out->name, sizeof(out->name), "%s", ROUTES[g.route].name);
+  out->kind = ROUTES[g.route].kind; out->jobs = g.own.count; out->cells = g.own.cells; out->algo_bytes = g.own.algo_bytes;
   out->ms = g.ms; out->t0_ms = g.t0_ms;
   return PGPU_OK;
 }

@@ -1874,8 +1874,6 @@ __device__ __forceinline__ void endpoint_epilogue(const DevJob& job, DevResult* 
 // its longest job.  The rare large row classes (BIG instances, a few hundred registers per lane) and
 // the one-job-per-workgroup kernels keep launches of their own.
 // ---------------------------------------------------------------------------------------------
-struct WaveSegs { int n; int start[MAX_WAVE_SEGS]; int count[MAX_WAVE_SEGS]; int family[MAX_WAVE_SEGS]; };
-
 constexpr size_t WAVE_JOBS_LDS = 4 * (size_t)TB_WIN_BYTES + 4 * (size_t)TB_PATH + 4 * 4 * 65 * sizeof(uint32_t);
 static_assert(WAVE_JOBS_LDS + 256 <= 40 * 1024, "four workgroups of dp_batch_kernel per CU (160 KB of LDS; 256 B are static)");
 
@@ -1960,8 +1958,6 @@ void align_fallback_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult
 // The roles with four waves let the upper four end at once (s_barrier only waits for the waves of
 // a workgroup that have not ended).  All roles share the dynamic LDS.
 // ---------------------------------------------------------------------------------------------
-struct BatchDesc { WaveSegs segs; int wave_blocks; int bc_start, bc_count, ac_start, ac_count, lc_start, lc_count; LcfIndexView ix; };
-
 __global__ __launch_bounds__(512)
 void dp_batch_kernel(const DevJob* __restrict__ jobs, const BatchDesc d, DevResult* __restrict__ results,
                      uint8_t* __restrict__ ws, uint8_t* __restrict__ strs) {
@@ -2223,28 +2219,28 @@ void borders_slow_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* 
 
 }  // namespace
 
-// What dp_batch_kernel leaves to launches of their own: ED, ALIGN, KBAND of the large row classes (all of
-// them BIG: see lev_any_dispatch), BORDERS above 64 rows whose LDS exceeds the batch's (R = 0, `max_rows`
-// sizes the dynamic LDS) or beyond 4096 rows, AFFIX beyond 4096 rows (R = ROW_CLASS_STRIPS).
-void launch_lev(int family, int R, uint32_t max_rows, const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws,
-                uint8_t* strs, hipStream_t st) {
-  if (njobs <= 0) return;
-  const dim3 g4((njobs + 3) / 4), b256(256);
-  switch (family) {
-    case KF_ED:    hipLaunchKernelGGL(lev_any_kernel<MODE_ED>, g4, b256, 0, st, jobs, njobs, res, ws, strs); break;
-    case KF_ALIGN: hipLaunchKernelGGL(lev_any_kernel<MODE_ALIGN>, g4, b256, 0, st, jobs, njobs, res, ws, strs); break;
-    case KF_KBAND: hipLaunchKernelGGL(lev_any_kernel<MODE_KBAND>, g4, b256, 0, st, jobs, njobs, res, ws, strs); break;
-    case KF_BORDERS:
-      if (R == (int)ROW_CLASS_STRIPS) {
-        hipLaunchKernelGGL(borders_slow_kernel, dim3(njobs), dim3(SLOW_BLOCK), 0, st, jobs, njobs, res, ws);
-      } else {
-        const size_t lds = (2 * (COOP_W - 1) * 128 + 4 * ((size_t)max_rows + 1)) * sizeof(uint32_t);
-        hipLaunchKernelGGL(borders_coop_any_kernel, dim3(njobs), dim3(512), lds, st, jobs, njobs, res);
-      }
-      break;
-    case KF_AFFIX: hipLaunchKernelGGL((lev_wave_kernel<64, MODE_AFFIX, true>), g4, b256, 0, st, jobs, njobs, res, ws); break;
-    default: break;
-  }
+// What dp_batch_kernel leaves to launches of their own (one launcher per stand-alone route of the plan builder's
+// table; a group that is launched is never empty).  ED, ALIGN, KBAND: the large row classes, all of them BIG
+// instances (see lev_any_dispatch).
+template <int MODE>
+static void launch_lev_any(const DpLaunch& l) {
+  hipLaunchKernelGGL(lev_any_kernel<MODE>, dim3((l.njobs + 3) / 4), dim3(256), 0, l.st, l.jobs, l.njobs, l.res, l.ws, l.strs);
+}
+void launch_ed_big(const DpLaunch& l) { launch_lev_any<MODE_ED>(l); }
+void launch_align_big(const DpLaunch& l) { launch_lev_any<MODE_ALIGN>(l); }
+void launch_kband_big(const DpLaunch& l) { launch_lev_any<MODE_KBAND>(l); }
+
+void launch_borders_slow(const DpLaunch& l) {
+  hipLaunchKernelGGL(borders_slow_kernel, dim3(l.njobs), dim3(SLOW_BLOCK), 0, l.st, l.jobs, l.njobs, l.res, l.ws);
+}
+
+void launch_borders_coop(const DpLaunch& l) {
+  const size_t lds = (2 * (COOP_W - 1) * 128 + 4 * ((size_t)l.max_rows + 1)) * sizeof(uint32_t);
+  hipLaunchKernelGGL(borders_coop_any_kernel, dim3(l.njobs), dim3(512), lds, l.st, l.jobs, l.njobs, l.res);
+}
+
+void launch_affix_strips(const DpLaunch& l) {
+  hipLaunchKernelGGL((lev_wave_kernel<64, MODE_AFFIX, true>), dim3((l.njobs + 3) / 4), dim3(256), 0, l.st, l.jobs, l.njobs, l.res, l.ws);
 }
 
 void launch_align_fallback(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st) {
@@ -2252,32 +2248,26 @@ void launch_align_fallback(const DevJob* jobs, int njobs, DevResult* res, uint8_
   hipLaunchKernelGGL(align_fallback_kernel, dim3(njobs), dim3(256), 0, st, jobs, njobs, res, ws, strs);
 }
 
-void launch_gap_slow(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st) {
-  if (njobs <= 0) return;
-  hipLaunchKernelGGL(gap_slow_kernel, dim3(njobs), dim3(SLOW_BLOCK), 0, st, jobs, njobs, res, ws, strs);
+void launch_gap_slow(const DpLaunch& l) {
+  hipLaunchKernelGGL(gap_slow_kernel, dim3(l.njobs), dim3(SLOW_BLOCK), 0, l.st, l.jobs, l.njobs, l.res, l.ws, l.strs);
 }
 
-void launch_gap(const DevJob* jobs, int njobs, DevResult* res, uint8_t* ws, uint8_t* strs, hipStream_t st) {
-  if (njobs <= 0) return;
-  hipLaunchKernelGGL(gap_any_kernel, dim3((njobs + 3) / 4), dim3(256), 0, st, jobs, njobs, res, ws, strs);
+void launch_gap_big(const DpLaunch& l) {
+  hipLaunchKernelGGL(gap_any_kernel, dim3((l.njobs + 3) / 4), dim3(256), 0, l.st, l.jobs, l.njobs, l.res, l.ws, l.strs);
 }
 
-void launch_lcf(const DevJob* jobs, int njobs, uint32_t max_chunks, uint32_t max_l2,
-                unsigned long long* keys, hipStream_t st) {
-  if (njobs <= 0) return;
+void launch_lcf(const DpLaunch& l) {
   // grid.y = job (<= 65535 per launch, the caller slices), grid.x strides over diagonal chunks
   // ... as many workgroups per job as it takes to fill the chip: after the suffix-array path took the ordinary
   // jobs, what comes here is a handful of long ones (an N in the EST prefix) -- 64 workgroups each left three
   // quarters of the CUs idle and made these launches the long pole of their batches
-  uint32_t want = 4096u / (uint32_t)njobs;
+  uint32_t want = 4096u / (uint32_t)l.njobs;
   if (want < 64u) want = 64u;
-  const uint32_t gx = max_chunks < want ? (max_chunks ? max_chunks : 1u) : want;
+  const uint32_t gx = l.max_chunks < want ? (l.max_chunks ? l.max_chunks : 1u) : want;
   // LDS: s2 (rounded to 16) + s1 tile (256 + l2 - 1), sized for the largest l2 of the launch
-  const size_t lds = ((max_l2 + 15u) & ~15u) + LCF_BLOCK + max_l2;
-  hipLaunchKernelGGL(lcf_kernel, dim3(gx, njobs), dim3(LCF_BLOCK), lds, st, jobs, njobs, keys);
+  const size_t lds = ((l.max_l2 + 15u) & ~15u) + LCF_BLOCK + l.max_l2;
+  hipLaunchKernelGGL(lcf_kernel, dim3(gx, l.njobs), dim3(LCF_BLOCK), lds, l.st, l.jobs, l.njobs, l.keys);
 }
-
-constexpr size_t DP_BATCH_MAX_LDS = 64 * 1024;
 
 size_t dp_batch_lds_bytes(bool wave_jobs, int bc_count, uint32_t bc_max_rows, int ac_count, int lc_count) {
   size_t lds = 16;
@@ -2288,25 +2278,11 @@ size_t dp_batch_lds_bytes(bool wave_jobs, int bc_count, uint32_t bc_max_rows, in
   return lds;
 }
 
-bool launch_dp_batch(const DevJob* jobs, int n_segs, const int* family, const int* start, const int* count,
-                     int bc_start, int bc_count, uint32_t bc_max_rows, int ac_start, int ac_count, int lc_start, int lc_count,
-                     DevResult* res, uint8_t* ws, uint8_t* strs, const LcfIndexView& ix, hipStream_t st) {
-  BatchDesc d;
-  d.ix = ix;
-  d.lc_start = lc_start; d.lc_count = lc_count > 0 ? lc_count : 0;
-  d.segs.n = 0;
-  int total = 0;
-  for (int k = 0; k < n_segs && d.segs.n < MAX_WAVE_SEGS; ++k) {
-    if (count[k] <= 0) continue;
-    d.segs.family[d.segs.n] = family[k]; d.segs.start[d.segs.n] = start[k]; d.segs.count[d.segs.n] = count[k]; ++d.segs.n;
-    total += count[k];
-  }
-  d.wave_blocks = (total + 3) / 4;
-  d.bc_start = bc_start; d.bc_count = bc_count > 0 ? bc_count : 0;
-  d.ac_start = ac_start; d.ac_count = ac_count > 0 ? ac_count : 0;
+bool launch_dp_batch(const DevJob* jobs, const BatchDesc& d, uint32_t bc_max_rows, DevResult* res, uint8_t* ws, uint8_t* strs,
+                     hipStream_t st) {
   const int blocks = d.bc_count + d.ac_count + d.lc_count + d.wave_blocks;
   if (blocks == 0) return true;
-  const size_t lds = dp_batch_lds_bytes(total > 0, d.bc_count, bc_max_rows, d.ac_count, d.lc_count);
+  const size_t lds = dp_batch_lds_bytes(d.wave_blocks > 0, d.bc_count, bc_max_rows, d.ac_count, d.lc_count);
   if (lds > DP_BATCH_MAX_LDS) return false;
   hipLaunchKernelGGL(dp_batch_kernel, dim3(blocks), dim3(512), lds, st, jobs, d, res, ws, strs);
   return true;

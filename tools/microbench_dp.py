@@ -1,8 +1,10 @@
 """GPU box: latency of a batch of one DP family, row count and job count (event time of each group).
 
 Usage: python tools/microbench_dp.py [reps]
-The groups of such a batch are `dp_batch` (the one launch of everything latency-bound) and the stand-alone
-long poles the library launches beside it (large row classes, strips, BORDERS beyond the batch's LDS, LCF).
+The groups of such a batch are `dp_batch` (the one launch of everything latency-bound) and the routes the library
+launches beside it (ROUTES in pgpu_api.hip): `gap_wave`, `lev_wave<ED>`, `lev_wave<KBAND>` (their
+large row classes), `lev_wave<ALIGN,strips>`, `lev_wave<AFFIX,strips>`, `gap_slow`, `borders_slow`, `borders_coop`
+(patterns beyond the batch's LDS) and `lcf`.
 Prints one line per case and group: family, rows x columns, jobs, group name, microseconds (median of reps),
 and ns per sweep step (rows-on-lanes sweeps take about rows/R + columns steps)."""
 import os
