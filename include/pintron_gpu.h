@@ -80,6 +80,42 @@ int pgpu_index_load(pgpu_ctx* ctx, const char* path, const char* genomic, size_t
 int pgpu_index_suffix_array(pgpu_ctx* ctx, const pgpu_index* idx, uint32_t* sa_out, size_t cap);
 
 /* ------------------------------------------------------------------------------------------ */
+/* exact occurrences -- the other thing a suffix tree of the genomic is for: where does this   */
+/* string occur, byte for byte, inside this stretch of the sequence.  Replaces the strstr()    */
+/* loop of search_small_exon (src/factorization-refinement.c:781-834), which scans a whole     */
+/* intron for every (offstart, offend) pair.                                                   */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint64_t pat_off;      /* pattern bytes at patterns + pat_off                          */
+  uint32_t pat_len;
+  uint32_t reserved;     /* must be 0                                                    */
+  uint32_t lo, hi;       /* only occurrences t with lo <= t and t + pat_len <= hi count  */
+} pgpu_find_query;       /* 24 bytes */
+
+/* One batched call, synchronous: it returns after the answers have been downloaded.
+ *  - An occurrence is equality of pat_len BYTES, exactly what strstr / memcmp see in the reference
+ *    (the strstr of src/factorization-refinement.c:794-795): case-sensitive, and 'N' is a letter like any
+ *    other -- NOT a wildcard here, unlike PGPU_DP_ALIGN / GAP / LCF.  Overlapping occurrences all count
+ *    (the reference goes on one byte behind each hit, :829).
+ *  - out_first[q]..out_first[q+1] delimits the answers of query q (n_queries + 1 entries); within a query the
+ *    positions are ascending (the order in which the strstr loop meets them); *n_out is the total (n_out may be
+ *    NULL).  When out_cap is too small the call returns PGPU_ENOSPC, has still filled out_first and *n_out, and
+ *    has written nothing to out.  out == NULL with out_cap == 0 asks for the counts alone (PGPU_OK when there is
+ *    no occurrence at all).
+ *  - hi is clamped to the length of the sequence.  lo > hi, pat_off + pat_len > patterns_len or reserved != 0 in
+ *    any query is PGPU_EINVAL for the whole call.  pat_len == 0, a pattern longer than its window, or a window
+ *    that lies behind the end of the sequence gives an empty answer, not an error.  n_queries == 0 is PGPU_OK
+ *    with *n_out = 0 and out_first[0] = 0.
+ *  - idx may come from pgpu_index_build or from pgpu_index_load. */
+int pgpu_index_find(pgpu_ctx* ctx, const pgpu_index* idx,
+                    const char* patterns, size_t patterns_len,
+                    const pgpu_find_query* queries, size_t n_queries,
+                    uint32_t* out, size_t out_cap, uint64_t* out_first, size_t* n_out);
+/* HIP-event time of the kernels of the calling thread's last pgpu_index_find on a context with timing on
+ * (pgpu_set_timing): k = 0 count + scan, 1 fill; 0 without timing or when the stage did not run */
+double pgpu_index_find_kernel_ms(int k);
+
+/* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */
 /* two low-complexity filters, in the order of the reference's per-position lists.            */

@@ -38,12 +38,18 @@ class Pairing(C.Structure):
     _fields_ = [("p", C.c_int32), ("t", C.c_int32), ("l", C.c_int32)]
 
 
-assert C.sizeof(DpJob) == 48 and C.sizeof(DpResult) == 48
+class FindQuery(C.Structure):       # pgpu_find_query
+    _fields_ = [("pat_off", C.c_uint64), ("pat_len", C.c_uint32), ("reserved", C.c_uint32),
+                ("lo", C.c_uint32), ("hi", C.c_uint32)]
+
+
+assert C.sizeof(DpJob) == 48 and C.sizeof(DpResult) == 48 and C.sizeof(FindQuery) == 24
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
     "pgpu_init", "pgpu_destroy", "pgpu_last_error", "pgpu_abi_version", "pgpu_set_timing", "pgpu_device_numa_node",
     "pgpu_index_build", "pgpu_index_destroy", "pgpu_index_suffix_array", "pgpu_index_save", "pgpu_index_load", "pgpu_pairings",
+    "pgpu_index_find", "pgpu_index_find_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -91,6 +97,10 @@ def lib():
         L.pgpu_index_save.argtypes = [vp, vp, C.c_char_p, C.c_char_p]
         L.pgpu_index_load.argtypes = [vp, C.c_char_p, C.c_char_p, sz, C.POINTER(vp)]
         L.pgpu_index_suffix_array.argtypes = [vp, vp, C.POINTER(C.c_uint32), sz]
+        L.pgpu_index_find.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(FindQuery), sz,
+                                      C.POINTER(C.c_uint32), sz, C.POINTER(u64), C.POINTER(sz)]
+        L.pgpu_index_find_kernel_ms.argtypes = [C.c_int]
+        L.pgpu_index_find_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -190,6 +200,51 @@ class Index:
         self.ctx.check(self.ctx.L.pgpu_index_suffix_array(
             self.ctx.h, self.h, sa.ctypes.data_as(C.POINTER(C.c_uint32)), self.n))
         return sa
+
+    def find_raw(self, blob: bytes, queries, n_queries: int, out=None):
+        """One pgpu_index_find call as it is: `queries` a ctypes array of FindQuery over the pattern bytes `blob`,
+        `out` a numpy uint32 array or None (counts alone).  Returns (rc, first[n_queries + 1], total)."""
+        import numpy as np
+        first = np.zeros(n_queries + 1, dtype=np.uint64)
+        total = C.c_size_t(0)
+        rc = self.ctx.L.pgpu_index_find(
+            self.ctx.h, self.h, blob, len(blob), queries, n_queries,
+            out.ctypes.data_as(C.POINTER(C.c_uint32)) if out is not None else None, len(out) if out is not None else 0,
+            first.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+        return rc, first, total.value
+
+    def find(self, patterns, windows=None):
+        """Exact occurrences (byte equality, no N wildcard) of every pattern inside its window (lo, hi) of the
+        sequence -- the whole sequence when windows is None: a list of ascending numpy uint32 arrays."""
+        import numpy as np
+        n = len(patterns)
+        if windows is None:
+            windows = [(0, self.n)] * n
+        if len(windows) != n:
+            raise ValueError("one window per pattern")
+        lens = np.fromiter((len(p) for p in patterns), dtype=np.uint64, count=n)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offs[1:])
+        q = np.zeros(n, dtype=np.dtype([("pat_off", "<u8"), ("pat_len", "<u4"), ("reserved", "<u4"),
+                                        ("lo", "<u4"), ("hi", "<u4")]))
+        q["pat_off"], q["pat_len"] = offs[:n], lens
+        if n:
+            w = np.asarray(windows, dtype=np.uint32).reshape(n, 2)
+            q["lo"], q["hi"] = w[:, 0], w[:, 1]
+        blob = b"".join(patterns)
+        qs = q.ctypes.data_as(C.POINTER(FindQuery))
+        rc, first, total = self.find_raw(blob, qs, n)             # counts, then the positions
+        if rc == PGPU_ENOSPC:
+            out = np.empty(total, dtype=np.uint32)
+            rc, first, total = self.find_raw(blob, qs, n, out)
+        else:
+            out = np.empty(0, dtype=np.uint32)
+        self.ctx.check(rc)
+        return [out[int(first[i]):int(first[i + 1])] for i in range(n)]
+
+    def find_kernel_ms(self):
+        """HIP-event times of the last find on this thread: {"count+scan": ms, "fill": ms}"""
+        return {"count+scan": self.ctx.L.pgpu_index_find_kernel_ms(0), "fill": self.ctx.L.pgpu_index_find_kernel_ms(1)}
 
     def close(self):
         if self.h:

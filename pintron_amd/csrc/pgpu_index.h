@@ -8,11 +8,17 @@
 const uint8_t* pgpu_index_genomic(const pgpu_index* idx);   // device pointer
 size_t pgpu_index_length(const pgpu_index* idx);
 
+// width of the k-mer interval table (klo / khi): 4^KTAB entries each, upper-case ACGT k-mers only; an absent
+// k-mer has klo == khi
+constexpr uint32_t KTAB = 8;
+constexpr uint32_t KTAB_ENTRIES = 1u << (2 * KTAB);
+
 // What the suffix-array form of find_longest_common_factor_dp needs (pgpu_dp_kernels.hip: lcfsa_wave_body):
 //   focc   first occurrence of every upper-case ACGT l-mer, l = 1..8 (table l at offset (4^l - 4) / 3;
 //          0xFFFFFFFF: the l-mer does not occur)
 //   rmq    sparse table of range minima over the suffix array: level j >= 1 at (j-1) * n holds
 //          min(sa[k .. k + 2^j)) for k + 2^j <= n; level 0 is the suffix array itself
+//   klo, khi  the k-mer interval table above; T, sa, n: the sequence (n bytes), its suffix array
 //   first_bad  position of the first character of the sequence that is not an upper-case A, C, G or T
 //          (n when there is none): prefixes up to there can be searched with exact matching alone
 struct LcfIndexView {

@@ -30,12 +30,10 @@
 
 #include "pgpu_index.h"
 
-// The first KTAB characters of a pattern position select the suffix-array interval of that
+// The first KTAB (pgpu_index.h) characters of a pattern position select the suffix-array interval of that
 // KTAB-mer from a table (2 x 4^KTAB x 4 B = 512 KB, L2-resident) instead of ~2 x 17 bisection
 // steps over the whole array; the bisection continues inside that interval (a handful of
 // suffixes) from character KTAB on.  Only upper-case ACGT k-mers are tabulated.
-constexpr uint32_t KTAB = 8;
-constexpr uint32_t KTAB_ENTRIES = 1u << (2 * KTAB);
 
 struct pgpu_index {
   uint8_t* d_gen = nullptr;
