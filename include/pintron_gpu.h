@@ -116,6 +116,70 @@ int pgpu_index_find(pgpu_ctx* ctx, const pgpu_index* idx,
 double pgpu_index_find_kernel_ms(int k);
 
 /* ------------------------------------------------------------------------------------------ */
+/* intron classes and the small-exon search -- what search_small_exon                          */
+/* (src/factorization-refinement.c:641-871) does with every occurrence: it classifies the two  */
+/* introns the occurrence would create (_classify_intron, :612-629, which is                   */
+/* classify_genomic_intron_start_end, src/classify-intron.c:95-229) and keeps the longest      */
+/* small exon whose two introns are both classified (:772-834).  Both are answered from        */
+/* classification tables of the index (the four 5' splice-site scores of every start, the      */
+/* branch-point verdict of every end), built on the device at the first of these calls on an   */
+/* index, built or loaded, and kept until pgpu_index_destroy; the index file does not hold     */
+/* them.  All three calls are synchronous like pgpu_index_find.                                */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct { uint32_t start, end; } pgpu_intron;      /* both inclusive, as the reference's */
+
+/* classify_genomic_intron_start_end (src/classify-intron.c:95-229), the class alone: out_type[i] = 0 U12, 1 U2,
+ * 2 not classified, for the intron genomic[start .. end].  Identical to the reference wherever the reference is
+ * defined; elsewhere: an intron is cut at the end of the sequence (end at or behind the last byte), end < start
+ * or start at or behind the end is the empty intron, a motif with a byte outside ACGTNacgtn scores -1.0.  Lower
+ * case counts like upper case and N like A, as in the reference.  No per-query error; n == 0 is PGPU_OK. */
+int pgpu_index_classify(pgpu_ctx* ctx, const pgpu_index* idx, const pgpu_intron* introns, size_t n,
+                        uint8_t* out_type);
+/* diagnostics, like pgpu_index_suffix_array: the table of 5' matrix k (0 GTAG-U12, 1 ATAC-U12, 2 GTAG-U2,
+ * 3 GCAG-U2), len + 1 doubles: what GetScoreOf5Prime*BySS (src/classify-intron.c:231-330) returns for every start,
+ * bit for bit.  PGPU_ENOSPC when cap < len + 1. */
+int pgpu_index_score5(pgpu_ctx* ctx, const pgpu_index* idx, int k, double* out, size_t cap);
+
+/* One query = one execution of the block at src/factorization-refinement.c:760-834: what is left of
+ * search_small_exon when the edit distances and common factors in front of it (PGPU_DP_ED / PGPU_DP_LCF) are known. */
+#define PGPU_SEXON_MAX_ELEN 64
+typedef struct {
+  uint64_t e_off;            /* efact = ests + e_off, elen bytes (the reference's efact, :761-763)          */
+  uint32_t elen;
+  uint32_t allgstart, allglen;   /* allgfact = genomic[allgstart .. allgstart + allglen)  (:766-768)        */
+  uint32_t f1slen, f2plen;   /* perfect-border lengths (:708-737)                                           */
+  uint32_t min_intron_len;   /* MAX(4, config->min_intron_length) (:742); < 4 is PGPU_EINVAL                */
+  uint32_t reserved;         /* must be 0                                                                   */
+  /* 4 bytes of padding follow (the struct is aligned to its uint64_t): their content is ignored            */
+} pgpu_sexon_query;          /* 40 bytes */
+typedef struct {
+  int32_t  status;           /* PGPU_OK, or PGPU_ERANGE: elen > PGPU_SEXON_MAX_ELEN                         */
+  uint32_t len;              /* max_sexon_len (:772); 0 = none found, every field below is 0 then           */
+  uint32_t offstart, offend; /* of the winner                                                               */
+  uint32_t gpos;             /* genomic position of the small exon's first base (= gcut1_2, :822)           */
+  uint32_t i1type, i2type;   /* classes of the two introns of the winner (0 U12, 1 U2)                      */
+  uint32_t pad;              /* 0 */
+} pgpu_sexon_result;         /* 32 bytes */
+
+/*  - The four gates of :743-758 (f1slen < 6, f2plen < 6, allglen < 2 * min_intron_len + 6, elen < 6) give len = 0,
+ *    not an error: the reference ends the search there.  allgstart + allglen > len of the sequence,
+ *    e_off + elen > ests_len, reserved != 0 or min_intron_len < 4 in any query is PGPU_EINVAL for the whole call.
+ *  - The loop bounds max_offstart and max_offend are those of :776-785.  For (offstart, offend) the pattern is
+ *    efact[offstart .. elen - offend); an occurrence counts when it starts at or behind
+ *    allgstart + offstart + min_intron_len and ends at or before allgstart + allglen - offend - min_intron_len.
+ *    Occurrences are byte equality as in pgpu_index_find: case-sensitive, N a letter, overlapping ones all count.
+ *  - The introns of an occurrence occ are i1 = [allgstart + offstart, occ - 1] and
+ *    i2 = [occ + pattern length, allgstart + allglen - offend - 1]; a candidate needs both classes != 2 (:805-809).
+ *  - The winner.  The reference replaces its best candidate on strictly greater length only (:816), so among the
+ *    candidates of maximal length the FIRST in loop order wins: the smallest offstart, then the smallest
+ *    occurrence (offend follows from the length). */
+int pgpu_index_small_exons(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                           const pgpu_sexon_query* q, size_t n, pgpu_sexon_result* out);
+/* HIP-event time of the kernel of the calling thread's last pgpu_index_small_exons on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_small_exons_kernel_ms(void);
+
+/* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */
 /* two low-complexity filters, in the order of the reference's per-position lists.            */

@@ -43,13 +43,35 @@ class FindQuery(C.Structure):       # pgpu_find_query
                 ("lo", C.c_uint32), ("hi", C.c_uint32)]
 
 
+class Intron(C.Structure):          # pgpu_intron: both ends inclusive
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32)]
+
+
+class SexonQuery(C.Structure):      # pgpu_sexon_query (36 bytes of fields, padded to 40 by its uint64)
+    _fields_ = [("e_off", C.c_uint64), ("elen", C.c_uint32), ("allgstart", C.c_uint32), ("allglen", C.c_uint32),
+                ("f1slen", C.c_uint32), ("f2plen", C.c_uint32), ("min_intron_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SexonResult(C.Structure):     # pgpu_sexon_result
+    _fields_ = [("status", C.c_int32), ("len", C.c_uint32), ("offstart", C.c_uint32), ("offend", C.c_uint32),
+                ("gpos", C.c_uint32), ("i1type", C.c_uint32), ("i2type", C.c_uint32), ("pad", C.c_uint32)]
+
+
+SEXON_MAX_ELEN = 64
+SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
+                     ("f2plen", "<u4"), ("min_intron_len", "<u4"), ("reserved", "<u4"), ("_pad", "<u4")]
+SEXON_RESULT_DTYPE = [("status", "<i4"), ("len", "<u4"), ("offstart", "<u4"), ("offend", "<u4"), ("gpos", "<u4"),
+                      ("i1type", "<u4"), ("i2type", "<u4"), ("pad", "<u4")]
+
 assert C.sizeof(DpJob) == 48 and C.sizeof(DpResult) == 48 and C.sizeof(FindQuery) == 24
+assert C.sizeof(Intron) == 8 and C.sizeof(SexonQuery) == 40 and C.sizeof(SexonResult) == 32
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
     "pgpu_init", "pgpu_destroy", "pgpu_last_error", "pgpu_abi_version", "pgpu_set_timing", "pgpu_device_numa_node",
     "pgpu_index_build", "pgpu_index_destroy", "pgpu_index_suffix_array", "pgpu_index_save", "pgpu_index_load", "pgpu_pairings",
     "pgpu_index_find", "pgpu_index_find_kernel_ms",
+    "pgpu_index_classify", "pgpu_index_score5", "pgpu_index_small_exons", "pgpu_index_small_exons_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -101,6 +123,11 @@ def lib():
                                       C.POINTER(C.c_uint32), sz, C.POINTER(u64), C.POINTER(sz)]
         L.pgpu_index_find_kernel_ms.argtypes = [C.c_int]
         L.pgpu_index_find_kernel_ms.restype = C.c_double
+        L.pgpu_index_classify.argtypes = [vp, vp, C.POINTER(Intron), sz, C.POINTER(C.c_uint8)]
+        L.pgpu_index_score5.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_double), sz]
+        L.pgpu_index_small_exons.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(SexonQuery), sz, C.POINTER(SexonResult)]
+        L.pgpu_index_small_exons_kernel_ms.argtypes = []
+        L.pgpu_index_small_exons_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -245,6 +272,53 @@ class Index:
     def find_kernel_ms(self):
         """HIP-event times of the last find on this thread: {"count+scan": ms, "fill": ms}"""
         return {"count+scan": self.ctx.L.pgpu_index_find_kernel_ms(0), "fill": self.ctx.L.pgpu_index_find_kernel_ms(1)}
+
+    def classify(self, starts, ends, ctx=None):
+        """Class of every intron [starts[i], ends[i]] (both inclusive): numpy uint8, 0 U12, 1 U2, 2 not classified.
+        `ctx`: another context that shares this index (default: the one it was made on)."""
+        import numpy as np
+        ctx = ctx or self.ctx
+        iv = np.empty((len(starts), 2), dtype=np.uint32)
+        iv[:, 0], iv[:, 1] = starts, ends
+        out = np.empty(len(iv), dtype=np.uint8)
+        ctx.check(ctx.L.pgpu_index_classify(ctx.h, self.h, iv.ctypes.data_as(C.POINTER(Intron)), len(iv),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def score5(self, k):
+        """The table of 5' splice-site matrix k (0..3): n + 1 float64, what GetScoreOf5Prime*BySS gives per start."""
+        import numpy as np
+        out = np.empty(self.n + 1, dtype=np.float64)
+        self.ctx.check(self.ctx.L.pgpu_index_score5(self.ctx.h, self.h, k, out.ctypes.data_as(C.POINTER(C.c_double)), len(out)))
+        return out
+
+    def small_exons_raw(self, ests: bytes, queries, n: int):
+        """One pgpu_index_small_exons call as it is: `queries` a numpy array of SEXON_QUERY_DTYPE (or a ctypes array of
+        SexonQuery).  Returns (rc, results as a numpy array of SEXON_RESULT_DTYPE)."""
+        import numpy as np
+        res = np.zeros(n, dtype=np.dtype(SEXON_RESULT_DTYPE))
+        qp = queries.ctypes.data_as(C.POINTER(SexonQuery)) if hasattr(queries, "ctypes") else queries
+        rc = self.ctx.L.pgpu_index_small_exons(self.ctx.h, self.h, ests, len(ests), qp, n,
+                                               res.ctypes.data_as(C.POINTER(SexonResult)))
+        return rc, res
+
+    def small_exons(self, ests: bytes, queries):
+        """The search loop of search_small_exon for every query: `queries` an iterable of
+        (e_off, elen, allgstart, allglen, f1slen, f2plen, min_intron_len) or a numpy array of SEXON_QUERY_DTYPE;
+        a numpy array of SEXON_RESULT_DTYPE comes back."""
+        import numpy as np
+        if not isinstance(queries, np.ndarray):
+            rows = list(queries)
+            q = np.zeros(len(rows), dtype=np.dtype(SEXON_QUERY_DTYPE))
+            for i, r in enumerate(rows):
+                q[i] = tuple(r) + (0, 0)
+            queries = q
+        rc, res = self.small_exons_raw(ests, queries, len(queries))
+        self.ctx.check(rc)
+        return res
+
+    def small_exons_kernel_ms(self):
+        return self.ctx.L.pgpu_index_small_exons_kernel_ms()
 
     def close(self):
         if self.h:

@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <mutex>
 #include <hip/hip_runtime.h>
 #include "../../include/pintron_gpu.h"
 
@@ -27,6 +28,12 @@ struct LcfIndexView {
 };
 LcfIndexView pgpu_index_lcf_view(const pgpu_index* idx);
 constexpr uint32_t LCF_FOCC_ENTRIES = 87380;      // 4 + 16 + ... + 4^8
+
+// Tables that are derived from the sequence on first use and then belong to the index (the classification tables
+// of pgpu_classify.hip): whoever needs them takes `mu`, builds when `tables` is still null, and leaves `release`
+// for pgpu_index_destroy.  An index is shared by many contexts, so two of them may ask at the same time.
+struct pgpu_index_lazy { std::mutex mu; void* tables = nullptr; void (*release)(void*) = nullptr; };
+pgpu_index_lazy* pgpu_index_lazy_slot(const pgpu_index* idx);
 
 // context helpers implemented in pgpu_api.hip
 hipStream_t pgpu_ctx_stream(pgpu_ctx* ctx);

@@ -55,6 +55,8 @@ struct pgpu_index {
   // (32 per word): what the pairing kernels compare on (PackedSeq); the bytes stay for the flagged stretches
   uint32_t* d_code = nullptr;
   uint32_t* d_bad = nullptr;
+  // made on first use by whoever needs them (pgpu_index.h); nothing is built or allocated for them here
+  mutable pgpu_index_lazy lazy;
 };
 
 LcfIndexView pgpu_index_lcf_view(const pgpu_index* idx) {
@@ -66,6 +68,7 @@ LcfIndexView pgpu_index_lcf_view(const pgpu_index* idx) {
 
 const uint8_t* pgpu_index_genomic(const pgpu_index* idx) { return idx->d_gen; }
 size_t pgpu_index_length(const pgpu_index* idx) { return idx->len; }
+pgpu_index_lazy* pgpu_index_lazy_slot(const pgpu_index* idx) { return &idx->lazy; }
 
 namespace {
 
@@ -807,6 +810,7 @@ extern "C" int pgpu_index_destroy(pgpu_ctx* ctx, pgpu_index* idx) {
   hipStreamSynchronize(pgpu_ctx_stream(ctx));
   hipFree(idx->d_gen); hipFree(idx->d_sa); hipFree(idx->d_lcp); hipFree(idx->d_klo); hipFree(idx->d_khi); hipFree(idx->d_key);
   hipFree(idx->d_focc); hipFree(idx->d_rmq); hipFree(idx->d_code); hipFree(idx->d_bad);
+  if (idx->lazy.tables && idx->lazy.release) idx->lazy.release(idx->lazy.tables);
   delete idx;
   return PGPU_OK;
 }
