@@ -180,6 +180,71 @@ int pgpu_index_small_exons(pgpu_ctx* ctx, const pgpu_index* idx, const char* est
 double pgpu_index_small_exons_kernel_ms(void);
 
 /* ------------------------------------------------------------------------------------------ */
+/* intron borders -- what refine_intron (src/refine-intron.c:47-265) does with the 3-state gap  */
+/* alignment of an intron (PGPU_DP_GAP, which stays a job of the caller): the canonical-site    */
+/* searches on the gapped rows (Find_*, :892-990, :1852-1972), the four shift heuristics with   */
+/* their edit distances (Shift_*, :992-1850), the Burset fallback (Try_Burset_after_match,      */
+/* :267-344) and the tests that accept or refuse the result (:123-155, :245-257).  One query =  */
+/* one intron; the call is synchronous and batched like pgpu_index_small_exons.                 */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct { int32_t EST_start, EST_end, GEN_start, GEN_end; } pgpu_factor;   /* the reference's _factor, inclusive; 16 bytes */
+
+#define PGPU_REFINE_MAX_DIM 1024      /* alignment columns per query; beyond: PGPU_ERANGE for that query */
+#define PGPU_REFINE_MAX_ED   256      /* bytes of one operand of an edit distance; beyond: PGPU_ERANGE for that query.
+                                         The default configuration's windows (30 + gap + 30 against 30 + 70 + 70 + 30)
+                                         cannot make a longer one: an operand is a piece of one window plus at most
+                                         16 bytes of the rows */
+#define PGPU_REFINE_FIRST_INTRON 1u   /* flags bit 0 */
+
+typedef struct {
+  uint64_t est_off;  uint32_t est_len;        /* est_info->EST_seq = ests + est_off, est_len bytes                          */
+  uint32_t flags;                              /* bit 0: first_intron; other bits must be 0                                  */
+  uint64_t rows_off; uint32_t dim;             /* EST_gap_alignment = rows + rows_off, GEN_gap_alignment = rows + rows_off + dim,
+                                                  dim bytes each (no terminator needed)                                      */
+  int32_t  factor_cut, intron_start, intron_end, intron_start_on_align, intron_end_on_align;   /* v[1..5] of the PGPU_DP_GAP result */
+  pgpu_factor donor, acceptor;                 /* the two exons as they are when the alignment's windows are cut             */
+  int32_t  suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen, min_intron_length;
+  /* offsets: est_off 0, est_len 8, flags 12, rows_off 16, dim 24, factor_cut 28 .. intron_end_on_align 44, donor 48,
+   * acceptor 64, suffpref_length_on_est 80 .. min_intron_length 92: no padding anywhere */
+} pgpu_refine_query;         /* 96 bytes */
+
+typedef struct {
+  int32_t status;                  /* PGPU_OK or PGPU_ERANGE (then refined = 0, path = 0, the factors unchanged)            */
+  int32_t refined;                 /* refine_intron's return value                                                           */
+  int32_t path;                    /* which branch decided, see below                                                        */
+  int32_t pad;                     /* 0 */
+  pgpu_factor donor, acceptor;     /* as refine_intron leaves them (unchanged when refined == 0)                             */
+} pgpu_refine_result;        /* 48 bytes */
+
+/*  - path: 0 donor attached, first intron (:127-135, refined 1); 1 donor attached, not the first intron (:136-140,
+ *    refined 0); 2 intron too small (:143, 0); 3 a border shifted by more than 20 (:151, 0); 4 already canonical (:189, 1);
+ *    5 Shift_right_to_left_1; 6 Shift_left_to_right_1; 7 Shift_right_to_left_2; 8 Shift_left_to_right_2; 9 Burset.  For
+ *    5 - 9 refined is 0 when the test of :245 refuses the borders.
+ *  - The call derives donor_suffix_left_on_est / _on_gen and deleted_intron_dim from the factors and the three lengths
+ *    (:55-64, :110) and from there does what the reference does, quirks included: the comparisons with "AG", "GT", "GC"
+ *    are case-sensitive, the Burset lookup is not; `error` and `edit_prev` of the two _1 routines are unsigned and wrap;
+ *    the mismatch count taken off the extended distances is the one of the GENOMIC eight-column piece; two cycles.
+ *    The edit distances are PGPU_DP_ED's (Levenshtein, N no wildcard).  All distances one Shift_* routine can ask for
+ *    (at most six) are computed together once its two cycles are known; an operand longer than PGPU_REFINE_MAX_ED among
+ *    them refuses the query.
+ *  - Where the reference's scans leave their strings: a row byte outside [0, dim) reads as 0; a 0 inside a row ends
+ *    it (strlen), and in an empty genomic row Find_AG_after_on_the_right finds nothing; a byte of the EST outside
+ *    [0, est_len) and a byte of the genomic sequence outside [0, its length) read as 0, and both strings end at their
+ *    terminator (real_substring stops there).
+ *  - PGPU_EINVAL for the whole call, in any query: est_off + est_len > ests_len or rows_off + 2 * dim > rows_len; an
+ *    unknown flag bit; dim == 0; donor.EST_end >= acceptor.EST_start or donor.GEN_end >= acceptor.GEN_start (the
+ *    my_asserts of :52-53); a coordinate that is no offset into what it indexes: a factor's EST_* outside
+ *    [-1, est_len], GEN_* outside [-1, length of the sequence], one of the five alignment values outside [0, dim], a
+ *    suffpref length that is negative or above 2^24 (min_intron_length is only compared: any value).  n == 0 is
+ *    PGPU_OK.  idx may be built or loaded. */
+int pgpu_index_refine_introns(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                              const char* rows, size_t rows_len,
+                              const pgpu_refine_query* q, size_t n, pgpu_refine_result* out);
+/* HIP-event time of the kernel of the calling thread's last pgpu_index_refine_introns on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_refine_introns_kernel_ms(void);
+
+/* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */
 /* two low-complexity filters, in the order of the reference's per-position lists.            */

@@ -57,6 +57,33 @@ class SexonResult(C.Structure):     # pgpu_sexon_result
                 ("gpos", C.c_uint32), ("i1type", C.c_uint32), ("i2type", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class Factor(C.Structure):         # pgpu_factor: the reference's _factor, all four inclusive
+    _fields_ = [("EST_start", C.c_int32), ("EST_end", C.c_int32), ("GEN_start", C.c_int32), ("GEN_end", C.c_int32)]
+
+
+class RefineQuery(C.Structure):    # pgpu_refine_query
+    _fields_ = [("est_off", C.c_uint64), ("est_len", C.c_uint32), ("flags", C.c_uint32), ("rows_off", C.c_uint64),
+                ("dim", C.c_uint32), ("factor_cut", C.c_int32), ("intron_start", C.c_int32), ("intron_end", C.c_int32),
+                ("intron_start_on_align", C.c_int32), ("intron_end_on_align", C.c_int32), ("donor", Factor), ("acceptor", Factor),
+                ("suffpref_length_on_est", C.c_int32), ("suffpref_length_for_intron", C.c_int32),
+                ("suffpref_length_on_gen", C.c_int32), ("min_intron_length", C.c_int32)]
+
+
+class RefineResult(C.Structure):   # pgpu_refine_result
+    _fields_ = [("status", C.c_int32), ("refined", C.c_int32), ("path", C.c_int32), ("pad", C.c_int32),
+                ("donor", Factor), ("acceptor", Factor)]
+
+
+REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
+_FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
+REFINE_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("flags", "<u4"), ("rows_off", "<u8"), ("dim", "<u4"),
+                      ("factor_cut", "<i4"), ("intron_start", "<i4"), ("intron_end", "<i4"), ("intron_start_on_align", "<i4"),
+                      ("intron_end_on_align", "<i4"), ("donor", _FACTOR_DTYPE), ("acceptor", _FACTOR_DTYPE),
+                      ("suffpref_length_on_est", "<i4"), ("suffpref_length_for_intron", "<i4"), ("suffpref_length_on_gen", "<i4"),
+                      ("min_intron_length", "<i4")]
+REFINE_RESULT_DTYPE = [("status", "<i4"), ("refined", "<i4"), ("path", "<i4"), ("pad", "<i4"), ("donor", _FACTOR_DTYPE),
+                       ("acceptor", _FACTOR_DTYPE)]
+
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
                      ("f2plen", "<u4"), ("min_intron_len", "<u4"), ("reserved", "<u4"), ("_pad", "<u4")]
@@ -65,6 +92,7 @@ SEXON_RESULT_DTYPE = [("status", "<i4"), ("len", "<u4"), ("offstart", "<u4"), ("
 
 assert C.sizeof(DpJob) == 48 and C.sizeof(DpResult) == 48 and C.sizeof(FindQuery) == 24
 assert C.sizeof(Intron) == 8 and C.sizeof(SexonQuery) == 40 and C.sizeof(SexonResult) == 32
+assert C.sizeof(Factor) == 16 and C.sizeof(RefineQuery) == 96 and C.sizeof(RefineResult) == 48
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -72,6 +100,7 @@ EXPORTS = [
     "pgpu_index_build", "pgpu_index_destroy", "pgpu_index_suffix_array", "pgpu_index_save", "pgpu_index_load", "pgpu_pairings",
     "pgpu_index_find", "pgpu_index_find_kernel_ms",
     "pgpu_index_classify", "pgpu_index_score5", "pgpu_index_small_exons", "pgpu_index_small_exons_kernel_ms",
+    "pgpu_index_refine_introns", "pgpu_index_refine_introns_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -128,6 +157,10 @@ def lib():
         L.pgpu_index_small_exons.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(SexonQuery), sz, C.POINTER(SexonResult)]
         L.pgpu_index_small_exons_kernel_ms.argtypes = []
         L.pgpu_index_small_exons_kernel_ms.restype = C.c_double
+        L.pgpu_index_refine_introns.argtypes = [vp, vp, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(RefineQuery), sz,
+                                                C.POINTER(RefineResult)]
+        L.pgpu_index_refine_introns_kernel_ms.argtypes = []
+        L.pgpu_index_refine_introns_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -319,6 +352,26 @@ class Index:
 
     def small_exons_kernel_ms(self):
         return self.ctx.L.pgpu_index_small_exons_kernel_ms()
+
+    def refine_introns_raw(self, ests: bytes, rows: bytes, queries, n: int):
+        """One pgpu_index_refine_introns call as it is: `queries` a numpy array of REFINE_QUERY_DTYPE (or a ctypes array
+        of RefineQuery).  Returns (rc, results as a numpy array of REFINE_RESULT_DTYPE)."""
+        import numpy as np
+        res = np.zeros(n, dtype=np.dtype(REFINE_RESULT_DTYPE))
+        qp = queries.ctypes.data_as(C.POINTER(RefineQuery)) if hasattr(queries, "ctypes") else queries
+        rc = self.ctx.L.pgpu_index_refine_introns(self.ctx.h, self.h, ests, len(ests), rows, len(rows), qp, n,
+                                                  res.ctypes.data_as(C.POINTER(RefineResult)))
+        return rc, res
+
+    def refine_introns(self, ests: bytes, rows: bytes, queries):
+        """refine_intron's decision for every query from its gap alignment (the rows and v[1..5] of a PGPU_DP_GAP job):
+        `queries` a numpy array of REFINE_QUERY_DTYPE; a numpy array of REFINE_RESULT_DTYPE comes back."""
+        rc, res = self.refine_introns_raw(ests, rows, queries, len(queries))
+        self.ctx.check(rc)
+        return res
+
+    def refine_introns_kernel_ms(self):
+        return self.ctx.L.pgpu_index_refine_introns_kernel_ms()
 
     def close(self):
         if self.h:
