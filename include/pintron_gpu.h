@@ -244,6 +244,66 @@ int pgpu_index_refine_introns(pgpu_ctx* ctx, const pgpu_index* idx, const char* 
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_refine_introns_kernel_ms(void);
 
+/* All of refine_intron, chained per EST: the loop of src/est-factorizations.c:446-490 over one factorization, with the
+ * window cutting (src/refine-intron.c:55-116), the 3-state gap alignment (compute_gap_alignment, :560-890) and the border
+ * decision above done on the device for one intron after the other.  Each call of the loop changes its acceptor, and that
+ * acceptor is the donor of the next call, so the windows of intron k + 1 exist only when intron k is settled: nothing of an
+ * intron leaves the device between its windows and its verdict.  One query = one factorization; the call is synchronous and
+ * batched like pgpu_index_refine_introns. */
+#define PGPU_CHAIN_MAX_EST_WINDOW 192   /* bytes of the EST window of one intron; beyond: PGPU_ERANGE for that chain            */
+#define PGPU_CHAIN_MAX_GEN_WINDOW 320   /* bytes of its genomic window.  The default configuration (30 + gap + 30 against
+                                           30 + 70 + 70 + 30) fits with an unaligned EST gap of up to 132 bytes               */
+typedef struct {
+  uint64_t est_off; uint32_t est_len;     /* est_info->EST_seq = ests + est_off, est_len bytes (at most 2^31 - 1)                */
+  uint32_t first_exon, n_exons;           /* the factorization = exons[first_exon .. first_exon + n_exons)                       */
+  uint32_t reserved;                      /* must be 0                                                                           */
+  int32_t  suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen, min_intron_length;
+  /* offsets: est_off 0, est_len 8, first_exon 12, n_exons 16, reserved 20, suffpref_length_on_est 24 .. min_intron_length 36:
+   * no padding anywhere */
+} pgpu_chain_query;          /* 40 bytes */
+
+typedef struct {
+  int32_t  status;        /* PGPU_OK, or PGPU_ERANGE: an intron did not fit the caps                                             */
+  uint32_t done;          /* introns settled (n_exons - 1 on PGPU_OK); on PGPU_ERANGE the index of the one refused: out_exons
+                             holds the chain as it stood BEFORE that intron and the caller goes on from there on its own path  */
+  uint32_t dropped_first; /* 1 when the rule of est-factorizations.c:476-485 removed the first exon (first and second exon
+                             begin at the same EST position; only when the whole chain was done): the exon stays in out_exons,
+                             the caller skips it                                                                                */
+  uint32_t pad;           /* 0 */
+} pgpu_chain_result;         /* 16 bytes: status 0, done 4, dropped_first 8, pad 12 */
+
+/*  - out_exons (n_exons_total entries) is parallel to exons: same indices; exons no query names are copied unchanged.
+ *    out_steps (n_exons_total bytes) is parallel too: for the exon at place i >= 1 of a chain, what pgpu_refine_result holds
+ *    for the intron in front of it -- path in bits 0-3, refined in bit 7; 0 for a chain's first exon and for introns never
+ *    reached.
+ *  - Per intron, in chain order, the call does refine_intron(config, gen, est, &exon[i], &exon[i + 1], i == 0) on the exons
+ *    as they are at that moment: the windows are the real_substring pieces of :55-116 with the clamping of
+ *    ef_gap_window_build (a negative index shortens the piece, a piece ends at the terminator -- the end of the EST, of the
+ *    sequence, or a 0 byte -- and a negative length is empty); the alignment is PGPU_DP_GAP's, bit for bit (the same rows,
+ *    the same five values); the decision is pgpu_index_refine_introns', with every quirk listed there.
+ *  - The reference overruns its own sequence_on_est block when the EST has an unaligned gap between the two exons (:84-87:
+ *    the block is sized for the donor's suffix and the acceptor's prefix, the gap is appended as well).  There the entry is
+ *    defined by the restatement: the strings as ef_gap_window_build makes them.
+ *  - n_exons == 1 is a chain with nothing to do (PGPU_OK, done 0).  n == 0 is PGPU_OK (out_exons = exons, out_steps = 0).
+ *  - Caps: a window longer than PGPU_CHAIN_MAX_EST_WINDOW / _GEN_WINDOW, or an edit-distance operand longer than
+ *    PGPU_REFINE_MAX_ED, ends THAT chain with PGPU_ERANGE as described at `done`; it never affects another chain.  (The
+ *    alignment of two windows within the caps has at most 512 columns: PGPU_REFINE_MAX_DIM cannot refuse.)
+ *  - PGPU_EINVAL for the whole call: n_exons == 0; first_exon + n_exons > n_exons_total or est_off + est_len > ests_len;
+ *    est_len > 2^31 - 1; reserved != 0; two chains share an exon; a factor coordinate outside what
+ *    pgpu_index_refine_introns accepts (EST_* outside [-1, est_len], GEN_* outside [-1, length of the sequence]); a suffpref
+ *    length outside [0, 2^24]; for some adjacent pair exon[i].EST_end >= exon[i + 1].EST_start or exon[i].GEN_end >=
+ *    exon[i + 1].GEN_start (the my_asserts of :52-53).  The last can be checked up front because it concerns fields no
+ *    earlier step writes: refining the pair (i - 1, i) changes EST_start and GEN_start of exon i alone, and EST_end and
+ *    GEN_end of exon i and the starts of exon i + 1 are written by the refinement of the pair (i, i + 1) itself.
+ *  - idx may be built or loaded. */
+int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                             const pgpu_factor* exons, size_t n_exons_total,
+                             const pgpu_chain_query* q, size_t n,
+                             pgpu_factor* out_exons, uint8_t* out_steps, pgpu_chain_result* out);
+/* HIP-event time of the kernel of the calling thread's last pgpu_index_refine_chains on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_refine_chains_kernel_ms(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */

@@ -74,7 +74,18 @@ class RefineResult(C.Structure):   # pgpu_refine_result
                 ("donor", Factor), ("acceptor", Factor)]
 
 
+class ChainQuery(C.Structure):     # pgpu_chain_query
+    _fields_ = [("est_off", C.c_uint64), ("est_len", C.c_uint32), ("first_exon", C.c_uint32), ("n_exons", C.c_uint32),
+                ("reserved", C.c_uint32), ("suffpref_length_on_est", C.c_int32), ("suffpref_length_for_intron", C.c_int32),
+                ("suffpref_length_on_gen", C.c_int32), ("min_intron_length", C.c_int32)]
+
+
+class ChainResult(C.Structure):    # pgpu_chain_result
+    _fields_ = [("status", C.c_int32), ("done", C.c_uint32), ("dropped_first", C.c_uint32), ("pad", C.c_uint32)]
+
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
+CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
 REFINE_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("flags", "<u4"), ("rows_off", "<u8"), ("dim", "<u4"),
                       ("factor_cut", "<i4"), ("intron_start", "<i4"), ("intron_end", "<i4"), ("intron_start_on_align", "<i4"),
@@ -83,6 +94,12 @@ REFINE_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("flags", "<u4"), 
                       ("min_intron_length", "<i4")]
 REFINE_RESULT_DTYPE = [("status", "<i4"), ("refined", "<i4"), ("path", "<i4"), ("pad", "<i4"), ("donor", _FACTOR_DTYPE),
                        ("acceptor", _FACTOR_DTYPE)]
+
+CHAIN_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u4"), ("reserved", "<u4"),
+                     ("suffpref_length_on_est", "<i4"), ("suffpref_length_for_intron", "<i4"), ("suffpref_length_on_gen", "<i4"),
+                     ("min_intron_length", "<i4")]
+CHAIN_RESULT_DTYPE = [("status", "<i4"), ("done", "<u4"), ("dropped_first", "<u4"), ("pad", "<u4")]
+FACTOR_DTYPE = _FACTOR_DTYPE
 
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
@@ -93,6 +110,7 @@ SEXON_RESULT_DTYPE = [("status", "<i4"), ("len", "<u4"), ("offstart", "<u4"), ("
 assert C.sizeof(DpJob) == 48 and C.sizeof(DpResult) == 48 and C.sizeof(FindQuery) == 24
 assert C.sizeof(Intron) == 8 and C.sizeof(SexonQuery) == 40 and C.sizeof(SexonResult) == 32
 assert C.sizeof(Factor) == 16 and C.sizeof(RefineQuery) == 96 and C.sizeof(RefineResult) == 48
+assert C.sizeof(ChainQuery) == 40 and C.sizeof(ChainResult) == 16
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -101,6 +119,7 @@ EXPORTS = [
     "pgpu_index_find", "pgpu_index_find_kernel_ms",
     "pgpu_index_classify", "pgpu_index_score5", "pgpu_index_small_exons", "pgpu_index_small_exons_kernel_ms",
     "pgpu_index_refine_introns", "pgpu_index_refine_introns_kernel_ms",
+    "pgpu_index_refine_chains", "pgpu_index_refine_chains_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -161,6 +180,10 @@ def lib():
                                                 C.POINTER(RefineResult)]
         L.pgpu_index_refine_introns_kernel_ms.argtypes = []
         L.pgpu_index_refine_introns_kernel_ms.restype = C.c_double
+        L.pgpu_index_refine_chains.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(ChainQuery), sz,
+                                               C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(ChainResult)]
+        L.pgpu_index_refine_chains_kernel_ms.argtypes = []
+        L.pgpu_index_refine_chains_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -372,6 +395,30 @@ class Index:
 
     def refine_introns_kernel_ms(self):
         return self.ctx.L.pgpu_index_refine_introns_kernel_ms()
+
+    def refine_chains_raw(self, ests: bytes, exons, queries, n: int):
+        """One pgpu_index_refine_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+        CHAIN_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of CHAIN_RESULT_DTYPE)."""
+        import numpy as np
+        out_exons = np.zeros(len(exons), dtype=np.dtype(FACTOR_DTYPE))
+        out_steps = np.zeros(len(exons), dtype=np.uint8)
+        res = np.zeros(n, dtype=np.dtype(CHAIN_RESULT_DTYPE))
+        rc = self.ctx.L.pgpu_index_refine_chains(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)),
+                                                 len(exons), queries.ctypes.data_as(C.POINTER(ChainQuery)), n,
+                                                 out_exons.ctypes.data_as(C.POINTER(Factor)),
+                                                 out_steps.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 res.ctypes.data_as(C.POINTER(ChainResult)))
+        return rc, out_exons, out_steps, res
+
+    def refine_chains(self, ests: bytes, exons, queries):
+        """The reference's refinement loop over every factorization `queries` names (windows, gap alignment and border
+        decision per intron, chained on the device): (out_exons, out_steps, results) as numpy arrays."""
+        rc, out_exons, out_steps, res = self.refine_chains_raw(ests, exons, queries, len(queries))
+        self.ctx.check(rc)
+        return out_exons, out_steps, res
+
+    def refine_chains_kernel_ms(self):
+        return self.ctx.L.pgpu_index_refine_chains_kernel_ms()
 
     def close(self):
         if self.h:
