@@ -6,16 +6,36 @@ import pytest
 
 import dp_cases as D
 import golden_cases as G
+import route_lib as RL
 
 pytestmark = pytest.mark.gpu
 
 
+def run_with_groups(ctx, jl, index=None):
+    """capi.run_jobs, and the plan's census beside the answers: [(group name, jobs with a launch of their own)]"""
+    import pintron_amd.capi as capi
+    plan = capi.Plan(ctx, jl, index)
+    try:
+        plan.launch()
+        plan.sync()
+        res, strings = plan.fetch()
+        return [capi.decode(jl.jobs[i].kind, res[i], strings) for i in range(plan.n)], [(g["name"], g["jobs"]) for g in plan.groups()]
+    finally:
+        plan.close()
+
+
 def run_and_check(ctx, O, cases, expected=None):
+    """every answer against the oracle (or `expected`); returns the census of the plan that ran"""
     import pintron_amd.capi as capi
     jl = capi.JobList()
     for c in cases:
         c.add_to(jl)
-    out = capi.run_jobs(ctx, jl)
+    out, census = run_with_groups(ctx, jl)
+    check_answers(O, cases, out, expected)
+    return census
+
+
+def check_answers(O, cases, out, expected=None):
     bad = []
     for i, (c, got) in enumerate(zip(cases, out)):
         exp = expected[i] if expected is not None else c.expected(O)
@@ -118,7 +138,7 @@ def test_slow_kernels_beyond_the_fast_row_limits(gpu_ctx, O):
         t = D.mutate(rng, a[:cut], 0.02) + b"GT" + D.rand_seq(rng, extra) + b"AG" + D.mutate(rng, a[cut:], 0.02)
         cases.append(D.Case(D.BORDERS, a, t, p0=0, p1=n, p2=errs))
         cases.append(D.Case(D.BORDERS, a, t, p0=n // 3, p1=2 * n // 3, p2=errs, b_tail=b"GT"))
-    run_and_check(gpu_ctx, O, cases)
+    assert run_and_check(gpu_ctx, O, cases) == [("gap_slow", 4), ("borders_slow", 6)]
 
 
 def test_strips_beyond_4096_rows(gpu_ctx, O):
@@ -138,7 +158,9 @@ def test_strips_beyond_4096_rows(gpu_ctx, O):
     big = D.rand_seq(rng, 6000)
     cases.append(D.Case(D.ALIGN, big, big))                  # identity shortcut at that size
     cases.append(D.Case(D.ALIGN, big, b""))
-    run_and_check(gpu_ctx, O, cases)
+    census = run_and_check(gpu_ctx, O, cases)
+    assert census == RL.expected_groups(cases)["groups"]
+    assert dict(census)["lev_wave<ALIGN,strips>"] == 8 and dict(census)["lev_wave<AFFIX,strips>"] == 6
 
 
 def test_cooperative_kernels_at_class_boundaries(gpu_ctx, O):
@@ -159,7 +181,11 @@ def test_cooperative_kernels_at_class_boundaries(gpu_ctx, O):
                 cases.append(D.Case(D.BORDERS, a, t, p0=lo, p1=hi, p2=rng.choice([0, 3, len(a) // 10 + 1, len(a)]),
                                     b_tail=rng.choice([b"", b"A", b"GT"])))
         cases.append(D.Case(D.BORDERS, a, t[: max(1, len(t) // 5)], p0=0, p1=len(a), p2=2))
-    run_and_check(gpu_ctx, O, cases)
+    census = run_and_check(gpu_ctx, O, cases)
+    # the 4095- and 4096-row patterns take every cooperative BORDERS job of this plan out of the batch launch
+    # (tests/test_gpu_routes.py runs the role inside it up to its last row count); affix_coop is a role of it
+    assert census == RL.expected_groups(cases)["groups"]
+    assert dict(census)["borders_coop"] == sum(1 for c in cases if c.kind == D.BORDERS and len(c.a) > 64) and dict(census)["affix_coop"] == 0
 
 
 def test_lcf_genomic_scale(gpu_ctx, O):
@@ -245,7 +271,8 @@ def test_kband_band_on_lanes(gpu_ctx, O):
     cases.append(D.Case(D.KBAND, a, a[7:], p0=7))              # the result sits on the last slot of the band
     cases.append(D.Case(D.KBAND, a[7:], a, p0=7))
     cases.append(D.Case(D.KBAND, a, D.rand_seq(rng, 400), p0=20))   # unrelated: far above the bound
-    run_and_check(gpu_ctx, O, cases)
+    census = run_and_check(gpu_ctx, O, cases)
+    assert census == RL.expected_groups(cases)["groups"] and [n for n, _ in census] == ["lev_wave<KBAND>", "dp_batch"]
 
 
 def test_exon_check_dust_flags_beside_the_banded_distance(gpu_ctx, O):
@@ -325,7 +352,11 @@ def test_align_inside_a_band(gpu_ctx, O):
         cases.append(D.Case(D.ALIGN, b"A" * (n - 3), b"A" * n))
         cases.append(D.Case(D.ALIGN, D.mutate(rng, lc, 0.05), lc))
         cases.append(D.Case(D.ALIGN, b"N" * n, D.rand_seq(rng, n + 5)))
-    run_and_check(gpu_ctx, O, cases)
+    census = run_and_check(gpu_ctx, O, cases)
+    assert census == RL.expected_groups(cases)["groups"]
+    banded = [c for c in cases if RL.route_of(c)[0] == "align_band"]
+    assert ("align_band", 0) in census and len(banded) > len(cases) // 2
+    assert {c.expected(O)["score"] <= RL.ALIGN_BAND_HALF for c in banded} == {True, False}      # settled, and not
 
 
 def test_results_to_device(gpu_ctx, O):
@@ -428,9 +459,10 @@ def test_lcf_from_the_suffix_array(O, case_set):
                         s2[rng.choice([0, len(s2) - 1, rng.randrange(len(s2))])] = ord("n") if it % 6 == 1 else ord("N")
                         if it % 15 == 1 and len(s2) >= 2:
                             s2[rng.randrange(len(s2))] = ord("N")
-                    cases.append(D.Case(D.LCF, mixed[:G], bytes(s2)))
+                    cases.append(RL.GenCase(D.LCF, mixed[:G], bytes(s2)))
                     jl.add(capi.LCF, mixed[:G], bytes(s2), a_gen_off=0)
-                out = capi.run_jobs(ctx, jl, idx)
+                out, census = run_with_groups(ctx, jl, idx)
+                assert census == RL.expected_groups(cases, RL.index_info_of(mixed))["groups"] and ("lcf_sa", 0) in census
                 bad = [(len(c.a), c.b, got, c.expected(O)) for c, got in zip(cases, out) if not D.check_case(c, got, O)]
                 assert not bad, (kind, n, len(bad), bad[0])
             finally:
