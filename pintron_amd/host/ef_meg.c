@@ -30,6 +30,7 @@ ef_meg* ef_meg_from_pairings(const ef_triple* tr, size_t n_tr, size_t m) {
   ef_meg* V = (ef_meg*)malloc(sizeof(ef_meg));
   V->n = m + 2;
   V->rec = NULL; V->slab = false; V->lists = NULL;
+  V->diag_created = 0; V->diag_peak_list = 0;
   /* one list per EST position, most of them empty: headers exist only for the positions that
    * hold a vertex (source, sink and the distinct p of the pairings) */
   V->v = (ef_list**)malloc(V->n * sizeof(ef_list*) + (n_tr + 2) * sizeof(ef_list));
@@ -73,6 +74,7 @@ ef_meg* ef_meg_from_record(const void* rec, size_t m) {
   char* blk = (char*)malloc(bytes + 8);
   ef_meg* V = (ef_meg*)blk; blk += sizeof(ef_meg);
   V->n = n; V->rec = rec; V->slab = true; V->lists = NULL;
+  V->diag_created = 0; V->diag_peak_list = 0;
   V->v = (ef_list**)blk; blk += nv * sizeof(ef_list*);
   V->act = (size_t*)blk; blk += nv * sizeof(size_t);
   ef_list* heads = (ef_list*)blk; blk += nv * sizeof(ef_list);
@@ -103,7 +105,7 @@ ef_meg* ef_meg_from_record(const void* rec, size_t m) {
 }
 
 ef_meg* ef_meg_record_only(const void* rec, size_t m) {
-  ef_meg* V = (ef_meg*)calloc(1, sizeof(ef_meg));
+  ef_meg* V = (ef_meg*)calloc(1, sizeof(ef_meg));      /* the diagnostic counters are zero too */
   V->n = m + 2; V->rec = rec; V->slab = true;
   return V;
 }
@@ -324,10 +326,15 @@ void ef_compact_short_edges(ef_meg* V, const ef_config* cfg) {
           efi_remove(&a, NULL);
           efl_remove_first(x->incs, p);
           ef_pairing* nv = pairing_new(p->p, p->t, x->p + x->l - p->p);
+          ++V->diag_created;
+#define DIAG_PEAK(l_) do { if (efl_size(l_) > V->diag_peak_list) V->diag_peak_list = efl_size(l_); } while (0)
           ef_iter q = efl_begin(x->adjs);                       /* copy_adjacencies(new, a) */
-          while (efi_has_next(&q)) { ef_pairing* y = (ef_pairing*)efi_next(&q); efl_push_back(nv->adjs, y); efl_push_back(y->incs, nv); }
+          while (efi_has_next(&q)) { ef_pairing* y = (ef_pairing*)efi_next(&q); efl_push_back(nv->adjs, y); efl_push_back(y->incs, nv); DIAG_PEAK(y->incs); }
+          DIAG_PEAK(nv->adjs);
           q = efl_begin(p->incs);                               /* copy_incidencies(new, p) */
-          while (efi_has_next(&q)) { ef_pairing* y = (ef_pairing*)efi_next(&q); efl_push_back(nv->incs, y); efl_push_back(y->adjs, nv); }
+          while (efi_has_next(&q)) { ef_pairing* y = (ef_pairing*)efi_next(&q); efl_push_back(nv->incs, y); efl_push_back(y->adjs, nv); DIAG_PEAK(y->adjs); }
+          DIAG_PEAK(nv->incs);
+#undef DIAG_PEAK
           efl_push_back(V->v[i], nv);
         }
       }

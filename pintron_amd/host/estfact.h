@@ -154,6 +154,10 @@ typedef struct ef_meg_s {
    * graph that is one path is enumerated from it too (ef_fact.c: chain_embedding); the lists are built when
    * somebody asks (ef_meg_lists) */
   struct ef_meg_s* lists;
+  /* diagnostics that only ef_compact_short_edges maintains (they change no output): the vertices it created and
+   * the longest adjacency or incidence list it ever produced -- what a builder with fixed arrays has to hold at
+   * the peak, which counts taken when the compaction is over no longer show */
+  size_t diag_created, diag_peak_list;
 } ef_meg;
 
 /* first index k with act[k] >= lo */

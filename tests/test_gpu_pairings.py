@@ -88,31 +88,14 @@ def test_c3_shape_vs_oracle(gpu_ctx):
     oi.close()
 
 
-def _first_attempt_megs(tmp_path, genomic_fasta, ests_fasta):
-    """Host MEG code (checked against the reference's megs.txt in test_host_meg.py) + pairing oracle:
-    first-attempt graph of every prepared sequence."""
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    subprocess.run(["make", "-s", "-C", os.path.join(here, "hostcheck"), "meg_check"], check=True)
-    (tmp_path / "genomic.txt").write_text(genomic_fasta)
-    (tmp_path / "ests.txt").write_text(ests_fasta)
-    subprocess.run([os.path.join(here, "hostcheck", "meg_check")], cwd=tmp_path, check=True,
-                   env=dict(os.environ, MEG_CHECK_FIRST_ATTEMPT="1"), stderr=subprocess.DEVNULL)
-    out = []
-    for blk in (tmp_path / "megs-first.txt").read_text().split("@@end\n")[:-1]:
-        head, rest = blk.split("\n", 1)
-        cx, rest = rest.split("\n", 1)
-        meg, edges = rest.split("@@edges\n")
-        out.append(dict(seq=head[len("@@seq "):].encode(), complex=int(cx.split()[1]), meg=meg.encode(), edges=edges.encode()))
-    return out, (tmp_path / "genomic-prepared.txt").read_bytes()
-
-
 @pytest.mark.parametrize("source", ["c3", "ambn", "repeats"])
-def test_meg_stage_vs_host_meg_code(gpu_ctx, tmp_path, source):
+def test_meg_stage_vs_host_meg_code(gpu_ctx, source):
     """pgpu_pairing_plan_run_meg: for every prepared sequence (both strands) the finished graph --
     vertices in position-list order, adjacency in list order, the too_complex verdict and the two
-    texts est-fact prints -- against the host MEG code over the pairing oracle."""
-    import pintron_amd.capi as capi
+    texts est-fact prints -- against the host MEG code over the pairing oracle.  A record may be
+    flagged PGPU_MEG_UNAVAILABLE only where the host construction exceeds a cap of the kernel, and
+    must be where it does (the rule: tests/meg_lib.py); the records the rule cannot decide are counted."""
+    import meg_lib as M
     from pintron_amd import synth
     if source == "c3":
         w = synth.make("C3", n_est=400, seed=21)
@@ -122,29 +105,14 @@ def test_meg_stage_vs_host_meg_code(gpu_ctx, tmp_path, source):
     else:
         gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ambn")
         gfa, efa = open(os.path.join(gold, "genomic.txt")).read(), open(os.path.join(gold, "ests.txt")).read()
-    exp, genomic = _first_attempt_megs(tmp_path, gfa, efa)
+    exp, genomic = M.first_attempt_megs(gfa, efa)
     assert len(exp) >= 40
-    idx = capi.Index(gpu_ctx, genomic)
-    plan = capi.PairingPlan(gpu_ctx, idx, [e["seq"] for e in exp])
-    plan.run(15, 0.2)
-    plan.run_meg()
-    recs = [capi.parse_meg_record(r) for r in plan.fetch_meg()]
-    plan.close()
-    idx.close()
-    n_unavailable = 0
-    for e, r in zip(exp, recs):
-        if r["flags"] & 2:
-            n_unavailable += 1
-            continue
-        assert (r["flags"] & 1) == e["complex"]
-        assert r["meg_text"] == e["meg"] and r["edges_text"] == e["edges"]
-        # the structured part says what the text says
-        lines = e["meg"].decode().split("#adj#\n")
-        verts = [tuple(int(x) for x in ln.strip("()").split(",")) for ln in lines[0].splitlines()]
-        assert [tuple(v) for v in r["vertices"]] == verts
-        edges = [tuple(int(x) for x in ln.split("-")) for ln in lines[1].splitlines()]
-        assert [(k, t) for k, a in enumerate(r["adj"]) for t in a] == edges
+    recs = M.device_records(gpu_ctx, genomic, [e["seq"] for e in exp], M.DEFAULTS)
+    n_grey = M.check_records(exp, recs, M.DEFAULTS, source)
+    n_unavailable = sum(r["flags"] & 2 != 0 for r in recs)
+    print("%s: %d records, %d unavailable, %d grey" % (source, len(exp), n_unavailable, n_grey))
     assert n_unavailable * 20 <= len(exp)
+    assert n_grey * 20 <= len(exp)
 
 
 def test_index_file_roundtrip(gpu_ctx, tmp_path):
