@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "pgpu_internal.h"
+#include "pgpu_query_call.h"
 #include "pgpu_wave_dp.h"
 #include "pgpu_refine_body.h"
 
@@ -159,31 +160,9 @@ void chain_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __re
 
 thread_local double t_chain_ms = 0.0;
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// device buffers and events of one call: freed whichever way the call ends (as pgpu_refine.hip)
-struct CallBuffers {
-  uint8_t* d = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; hipStream_t st; bool failed = false;
-  explicit CallBuffers(hipStream_t s) : st(s) {}
-  ~CallBuffers() {
-    if (failed) (void)hipStreamSynchronize(st);            // nothing of this call may outlive its buffers
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(d);
-  }
-};
-
-bool coordinate_ok(int32_t v, size_t len) { return v >= -1 && (v < 0 || (size_t)v <= len); }
-
 constexpr unsigned WAVES_PER_CU = 16;       // resident chains per compute unit the grid is sized for
 
 }  // namespace
-
-#define TRY_HIP(call)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) { cb.failed = true;                                                \
-      return pgpu_ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PGPU_ENOMEM : PGPU_EDEVICE, hipGetErrorString(e_)); } \
-  } while (0)
 
 extern "C" double pgpu_index_refine_chains_kernel_ms(void) { return t_chain_ms; }
 
@@ -191,6 +170,7 @@ extern "C" int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, co
                                         const pgpu_factor* exons, size_t n_exons_total,
                                         const pgpu_chain_query* q, size_t n,
                                         pgpu_factor* out_exons, uint8_t* out_steps, pgpu_chain_result* out) {
+  t_chain_ms = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
   static_assert(sizeof(pgpu_chain_query) == 40 && sizeof(pgpu_chain_result) == 16 && sizeof(pgpu_factor) == 16, "ABI layout");
   if (!ctx || !idx || (n && (!q || !out)) || (ests_len && !ests) || (n_exons_total && (!exons || !out_exons || !out_steps)))
     return PGPU_EINVAL;
@@ -204,13 +184,11 @@ extern "C" int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, co
   for (size_t i = 0; i < n; ++i) {
     const pgpu_chain_query& x = q[i];
     bool ok = x.est_off <= ests_len && x.est_len <= ests_len - x.est_off && x.est_len <= 0x7fffffffu && x.reserved == 0 &&
-              x.n_exons != 0 && x.first_exon <= n_exons_total && x.n_exons <= n_exons_total - x.first_exon;
-    for (int32_t v : { x.suffpref_length_on_est, x.suffpref_length_for_intron, x.suffpref_length_on_gen })
-      ok = ok && v >= 0 && v <= (1 << 24);
+              x.n_exons != 0 && x.first_exon <= n_exons_total && x.n_exons <= n_exons_total - x.first_exon &&
+              suffpref_ok(x.suffpref_length_on_est, x.suffpref_length_for_intron, x.suffpref_length_on_gen);
     for (uint32_t k = 0; ok && k < x.n_exons; ++k) {
       const pgpu_factor& f = exons[x.first_exon + k];
-      ok = !named[x.first_exon + k] && coordinate_ok(f.EST_start, x.est_len) && coordinate_ok(f.EST_end, x.est_len) &&
-           coordinate_ok(f.GEN_start, glen) && coordinate_ok(f.GEN_end, glen);
+      ok = !named[x.first_exon + k] && factor_ok(f, x.est_len, glen);
       named[x.first_exon + k] = 1;
       if (ok && k + 1 < x.n_exons) {                       // the my_asserts of :52-53, on fields no earlier step writes
         const pgpu_factor& g = exons[x.first_exon + k + 1];
@@ -222,16 +200,13 @@ extern "C" int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, co
                                              "share, a donor that is not in front of its acceptor, or a coordinate outside what it "
                                              "indexes)");
   }
-  t_chain_ms = 0.0;
   if (n == 0) {
     if (n_exons_total) { memcpy(out_exons, exons, n_exons_total * sizeof(pgpu_factor)); memset(out_steps, 0, n_exons_total); }
     return PGPU_OK;
   }
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
-  hipStream_t st = pgpu_ctx_stream(ctx);
-  CallBuffers cb(st);
-  pgpu_range_push("refine chains");
-  struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
+  QueryCall call(ctx, "refine chains");
+  const hipStream_t st = call.st;
   int dev = 0, cus = 0;
   TRY_HIP(hipGetDevice(&dev));
   TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -240,24 +215,24 @@ extern "C" int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, co
   const size_t o_ex = up256(ests_len + 64), o_q = o_ex + up256(ex_bytes), o_oex = o_q + up256(n * sizeof(pgpu_chain_query)),
                o_st = o_oex + up256(ex_bytes), o_r = o_st + up256(n_exons_total), o_ws = o_r + up256(n * sizeof(pgpu_chain_result)),
                total = o_ws + waves * WS_WAVE;
-  TRY_HIP(hipMalloc((void**)&cb.d, total));
-  if (pgpu_ctx_timing(ctx)) for (auto& e : cb.ev) TRY_HIP(hipEventCreate(&e));
-  if (ests_len) TRY_HIP(hipMemcpyAsync(cb.d, ests, ests_len, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(cb.d + o_ex, exons, ex_bytes, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(cb.d + o_q, q, n * sizeof(pgpu_chain_query), hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMalloc((void**)&call.d, total));
+  TRY_HIP(call.timing_events(1));
+  if (ests_len) TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_ex, exons, ex_bytes, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof(pgpu_chain_query), hipMemcpyHostToDevice, st));
   // exons no query names: the output starts as a copy of the input, and their steps as 0
-  TRY_HIP(hipMemcpyAsync(cb.d + o_oex, cb.d + o_ex, ex_bytes, hipMemcpyDeviceToDevice, st));
-  TRY_HIP(hipMemsetAsync(cb.d + o_st, 0, n_exons_total, st));
-  if (cb.ev[0]) TRY_HIP(hipEventRecord(cb.ev[0], st));
-  hipLaunchKernelGGL(chain_kernel, dim3((unsigned)waves), dim3(64), 0, st, pgpu_index_genomic(idx), (uint32_t)glen, cb.d,
-                     (const pgpu_factor*)(cb.d + o_ex), (const pgpu_chain_query*)(cb.d + o_q), (uint32_t)n, cb.d + o_ws,
-                     (pgpu_factor*)(cb.d + o_oex), cb.d + o_st, (pgpu_chain_result*)(cb.d + o_r));
-  if (cb.ev[1]) TRY_HIP(hipEventRecord(cb.ev[1], st));
-  TRY_HIP(hipMemcpyAsync(out_exons, cb.d + o_oex, ex_bytes, hipMemcpyDeviceToHost, st));
-  TRY_HIP(hipMemcpyAsync(out_steps, cb.d + o_st, n_exons_total, hipMemcpyDeviceToHost, st));
-  TRY_HIP(hipMemcpyAsync(out, cb.d + o_r, n * sizeof(pgpu_chain_result), hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_oex, call.d + o_ex, ex_bytes, hipMemcpyDeviceToDevice, st));
+  TRY_HIP(hipMemsetAsync(call.d + o_st, 0, n_exons_total, st));
+  TRY_HIP(call.record(0));
+  hipLaunchKernelGGL(chain_kernel, dim3((unsigned)waves), dim3(64), 0, st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
+                     (const pgpu_factor*)(call.d + o_ex), (const pgpu_chain_query*)(call.d + o_q), (uint32_t)n, call.d + o_ws,
+                     (pgpu_factor*)(call.d + o_oex), call.d + o_st, (pgpu_chain_result*)(call.d + o_r));
+  TRY_HIP(call.record(1));
+  TRY_HIP(hipMemcpyAsync(out_exons, call.d + o_oex, ex_bytes, hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMemcpyAsync(out_steps, call.d + o_st, n_exons_total, hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMemcpyAsync(out, call.d + o_r, n * sizeof(pgpu_chain_result), hipMemcpyDeviceToHost, st));
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
-  if (cb.ev[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, cb.ev[0], cb.ev[1]); t_chain_ms = ms; }
+  call.elapsed_ms(0, &t_chain_ms);
   return PGPU_OK;
 }

@@ -21,6 +21,7 @@
 
 #include "pgpu_classify.h"
 #include "pgpu_pwm_data.h"
+#include "pgpu_query_call.h"
 
 namespace {
 
@@ -207,7 +208,7 @@ int class_tables_get(pgpu_ctx* ctx, const pgpu_index* idx, const ClassTables** o
   delete host;
   if (e != hipSuccess) {
     class_tables_release(t);
-    return pgpu_ctx_fail(ctx, e == hipErrorOutOfMemory ? PGPU_ENOMEM : PGPU_EDEVICE, hipGetErrorString(e));
+    return pgpu_ctx_fail(ctx, pgpu_code_of(e), hipGetErrorString(e));
   }
   slot->release = class_tables_release;
   slot->tables = t;
@@ -222,27 +223,7 @@ ClassView class_view(const ClassTables* t) {
 
 thread_local double t_sexon_ms = 0.0;
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// device buffers and events of one call: freed whichever way the call ends
-struct CallBuffers {
-  uint8_t* d = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; hipStream_t st; bool failed = false;
-  explicit CallBuffers(hipStream_t s) : st(s) {}
-  ~CallBuffers() {
-    if (failed) (void)hipStreamSynchronize(st);            // nothing of this call may outlive its buffers
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(d);
-  }
-};
-
 }  // namespace
-
-#define TRY_HIP(call)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) { cb.failed = true;                                                \
-      return pgpu_ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PGPU_ENOMEM : PGPU_EDEVICE, hipGetErrorString(e_)); } \
-  } while (0)
 
 extern "C" double pgpu_index_small_exons_kernel_ms(void) { return t_sexon_ms; }
 
@@ -254,14 +235,14 @@ extern "C" int pgpu_index_classify(pgpu_ctx* ctx, const pgpu_index* idx, const p
   const ClassTables* t = nullptr;
   int rc = class_tables_get(ctx, idx, &t);
   if (rc != PGPU_OK) return rc;
-  hipStream_t st = pgpu_ctx_stream(ctx);
-  CallBuffers cb(st);
+  QueryCall call(ctx, nullptr);                             // no range, no events
+  const hipStream_t st = call.st;
   const size_t o_out = up256(n * sizeof(pgpu_intron));
-  TRY_HIP(hipMalloc((void**)&cb.d, o_out + up256(n)));
-  TRY_HIP(hipMemcpyAsync(cb.d, introns, n * sizeof(pgpu_intron), hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMalloc((void**)&call.d, o_out + up256(n)));
+  TRY_HIP(hipMemcpyAsync(call.d, introns, n * sizeof(pgpu_intron), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, class_view(t),
-                     (const pgpu_intron*)cb.d, (uint32_t)n, cb.d + o_out);
-  TRY_HIP(hipMemcpyAsync(out_type, cb.d + o_out, n, hipMemcpyDeviceToHost, st));
+                     (const pgpu_intron*)call.d, (uint32_t)n, call.d + o_out);
+  TRY_HIP(hipMemcpyAsync(out_type, call.d + o_out, n, hipMemcpyDeviceToHost, st));
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
   return PGPU_OK;
@@ -284,6 +265,7 @@ extern "C" int pgpu_index_score5(pgpu_ctx* ctx, const pgpu_index* idx, int k, do
 
 extern "C" int pgpu_index_small_exons(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
                                       const pgpu_sexon_query* q, size_t n, pgpu_sexon_result* out) {
+  t_sexon_ms = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
   if (!ctx || !idx || (n && (!q || !out)) || (ests_len && !ests)) return PGPU_EINVAL;
   if (n > 0x7fffffffull) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 queries in one call");
   const size_t glen = pgpu_index_length(idx);
@@ -293,29 +275,26 @@ extern "C" int pgpu_index_small_exons(pgpu_ctx* ctx, const pgpu_index* idx, cons
       return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad small-exon query (reserved != 0, min_intron_len < 4, or efact / allgfact leave "
                                              "their sequence)");
   }
-  t_sexon_ms = 0.0;
   if (n == 0) return PGPU_OK;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   const ClassTables* t = nullptr;
   int rc = class_tables_get(ctx, idx, &t);
   if (rc != PGPU_OK) return rc;
-  hipStream_t st = pgpu_ctx_stream(ctx);
-  CallBuffers cb(st);
-  pgpu_range_push("small_exons");
-  struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
+  QueryCall call(ctx, "small_exons");
+  const hipStream_t st = call.st;
   const size_t o_q = up256(ests_len + 64), o_r = o_q + up256(n * sizeof(pgpu_sexon_query)),
                total = o_r + up256(n * sizeof(pgpu_sexon_result));
-  TRY_HIP(hipMalloc((void**)&cb.d, total));
-  if (pgpu_ctx_timing(ctx)) for (auto& e : cb.ev) TRY_HIP(hipEventCreate(&e));
-  if (ests_len) TRY_HIP(hipMemcpyAsync(cb.d, ests, ests_len, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(cb.d + o_q, q, n * sizeof(pgpu_sexon_query), hipMemcpyHostToDevice, st));
-  if (cb.ev[0]) TRY_HIP(hipEventRecord(cb.ev[0], st));
-  hipLaunchKernelGGL(small_exons_kernel, dim3((unsigned)n), dim3(64), 0, st, pgpu_index_lcf_view(idx), class_view(t), cb.d,
-                     (const pgpu_sexon_query*)(cb.d + o_q), (pgpu_sexon_result*)(cb.d + o_r));
-  if (cb.ev[1]) TRY_HIP(hipEventRecord(cb.ev[1], st));
-  TRY_HIP(hipMemcpyAsync(out, cb.d + o_r, n * sizeof(pgpu_sexon_result), hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMalloc((void**)&call.d, total));
+  TRY_HIP(call.timing_events(1));
+  if (ests_len) TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof(pgpu_sexon_query), hipMemcpyHostToDevice, st));
+  TRY_HIP(call.record(0));
+  hipLaunchKernelGGL(small_exons_kernel, dim3((unsigned)n), dim3(64), 0, st, pgpu_index_lcf_view(idx), class_view(t), call.d,
+                     (const pgpu_sexon_query*)(call.d + o_q), (pgpu_sexon_result*)(call.d + o_r));
+  TRY_HIP(call.record(1));
+  TRY_HIP(hipMemcpyAsync(out, call.d + o_r, n * sizeof(pgpu_sexon_result), hipMemcpyDeviceToHost, st));
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
-  if (cb.ev[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, cb.ev[0], cb.ev[1]); t_sexon_ms = ms; }
+  call.elapsed_ms(0, &t_sexon_ms);
   return PGPU_OK;
 }

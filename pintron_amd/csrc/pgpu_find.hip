@@ -12,9 +12,8 @@
 //                Otherwise the interval's entries inside the window are gathered in LDS, sorted there (bitonic, one
 //                wave) and copied out.  Either way the work is bounded by the smaller of interval and window,
 //                unless the answer itself is larger than the LDS.
-#include <new>
-
 #include "pgpu_find.h"
+#include "pgpu_query_call.h"
 
 namespace {
 
@@ -119,22 +118,14 @@ void find_fill_kernel(const LcfIndexView ix, const uint8_t* __restrict__ pats, c
 
 thread_local double t_find_ms[2] = {0.0, 0.0};
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" double pgpu_index_find_kernel_ms(int k) { return (k == 0 || k == 1) ? t_find_ms[k] : 0.0; }
 
-#define TRY_HIP(call)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) { rc = pgpu_ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PGPU_ENOMEM : PGPU_EDEVICE, \
-                                               hipGetErrorString(e_)); goto done; }          \
-  } while (0)
-
 extern "C" int pgpu_index_find(pgpu_ctx* ctx, const pgpu_index* idx, const char* patterns, size_t patterns_len,
                                const pgpu_find_query* queries, size_t n_queries,
                                uint32_t* out, size_t out_cap, uint64_t* out_first, size_t* n_out) {
+  t_find_ms[0] = t_find_ms[1] = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
   if (!ctx || !idx || !out_first || (n_queries && !queries) || (patterns_len && !patterns) || (!out && out_cap))
     return PGPU_EINVAL;
   if (n_queries > 0x7fffffffull) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 queries in one call");
@@ -143,65 +134,51 @@ extern "C" int pgpu_index_find(pgpu_ctx* ctx, const pgpu_index* idx, const char*
     if (q.reserved != 0 || q.lo > q.hi || q.pat_off > patterns_len || q.pat_len > patterns_len - q.pat_off)
       return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad find query (reserved != 0, lo > hi, or the pattern leaves the pattern buffer)");
   }
-  t_find_ms[0] = t_find_ms[1] = 0.0;
   if (n_out) *n_out = 0;
   out_first[0] = 0;
   if (n_queries == 0) return PGPU_OK;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
 
-  int rc = PGPU_OK;
-  hipStream_t st = pgpu_ctx_stream(ctx);
   const LcfIndexView ix = pgpu_index_lcf_view(idx);
   const size_t nq = n_queries;
   // one allocation for everything whose size is known up front; the positions follow once they are counted
   const size_t o_q = up256(patterns_len + 64), o_iv = o_q + up256(nq * sizeof(pgpu_find_query)),
                o_cnt = o_iv + up256(2 * nq * sizeof(uint32_t)), o_first = o_cnt + up256((nq + 1) * sizeof(uint32_t)),
                o_tmp = o_first + up256((nq + 1) * sizeof(unsigned long long)), total_bytes = o_tmp + up256(pgpu_scan_tmp_bytes(nq + 1));
-  uint8_t* d_base = nullptr;
-  uint32_t* d_out = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  unsigned long long total = 0;
   const dim3 grid((unsigned)nq), blk(64);
-  pgpu_range_push("find");
-  struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
-
-  TRY_HIP(hipMalloc((void**)&d_base, total_bytes));
-  {
-    uint8_t* d_pats = d_base;
-    pgpu_find_query* d_q = (pgpu_find_query*)(d_base + o_q);
-    uint32_t* d_iv = (uint32_t*)(d_base + o_iv);
-    uint32_t* d_cnt = (uint32_t*)(d_base + o_cnt);
-    unsigned long long* d_first = (unsigned long long*)(d_base + o_first);
-    void* d_tmp = d_base + o_tmp;
-    if (pgpu_ctx_timing(ctx)) for (auto& e : ev) TRY_HIP(hipEventCreate(&e));
-    if (patterns_len) TRY_HIP(hipMemcpyAsync(d_pats, patterns, patterns_len, hipMemcpyHostToDevice, st));
-    TRY_HIP(hipMemcpyAsync(d_q, queries, nq * sizeof(pgpu_find_query), hipMemcpyHostToDevice, st));
-    TRY_HIP(hipMemsetAsync(d_cnt + nq, 0, sizeof(uint32_t), st));
-    if (ev[0]) TRY_HIP(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(find_count_kernel, grid, blk, 0, st, ix, d_pats, d_q, d_iv, d_cnt);
-    pgpu_exclusive_scan_u32(d_cnt, d_first, nq + 1, d_tmp, st);
-    if (ev[1]) TRY_HIP(hipEventRecord(ev[1], st));
-    TRY_HIP(hipMemcpyAsync(out_first, d_first, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    TRY_HIP(pgpu_ctx_wait(ctx));
-    TRY_HIP(hipGetLastError());
-    total = out_first[nq];
-    if (n_out) *n_out = (size_t)total;
-    if (ev[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[0], ev[1]); t_find_ms[0] = ms; }
-    if (total > out_cap) { rc = pgpu_ctx_fail(ctx, PGPU_ENOSPC, "position buffer too small"); goto done; }
-    if (total) {
-      TRY_HIP(hipMalloc((void**)&d_out, (size_t)total * sizeof(uint32_t)));
-      if (ev[2]) TRY_HIP(hipEventRecord(ev[2], st));
-      hipLaunchKernelGGL(find_fill_kernel, grid, blk, 0, st, ix, d_pats, d_q, d_iv, d_first, d_out);
-      if (ev[3]) TRY_HIP(hipEventRecord(ev[3], st));
-      TRY_HIP(hipMemcpyAsync(out, d_out, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      TRY_HIP(pgpu_ctx_wait(ctx));
-      TRY_HIP(hipGetLastError());
-      if (ev[2]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[2], ev[3]); t_find_ms[1] = ms; }
-    }
-  }
-done:
-  if (rc != PGPU_OK && rc != PGPU_ENOSPC) (void)hipStreamSynchronize(st);     // nothing of this call may outlive its buffers
-  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  (void)hipFree(d_out); (void)hipFree(d_base);
-  return rc;
+  QueryCall call(ctx, "find");
+  const hipStream_t st = call.st;
+  TRY_HIP(hipMalloc((void**)&call.d, total_bytes));
+  uint8_t* d_pats = call.d;
+  pgpu_find_query* d_q = (pgpu_find_query*)(call.d + o_q);
+  uint32_t* d_iv = (uint32_t*)(call.d + o_iv);
+  uint32_t* d_cnt = (uint32_t*)(call.d + o_cnt);
+  unsigned long long* d_first = (unsigned long long*)(call.d + o_first);
+  void* d_tmp = call.d + o_tmp;
+  TRY_HIP(call.timing_events(2));
+  if (patterns_len) TRY_HIP(hipMemcpyAsync(d_pats, patterns, patterns_len, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(d_q, queries, nq * sizeof(pgpu_find_query), hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemsetAsync(d_cnt + nq, 0, sizeof(uint32_t), st));
+  TRY_HIP(call.record(0));
+  hipLaunchKernelGGL(find_count_kernel, grid, blk, 0, st, ix, d_pats, d_q, d_iv, d_cnt);
+  pgpu_exclusive_scan_u32(d_cnt, d_first, nq + 1, d_tmp, st);
+  TRY_HIP(call.record(1));
+  TRY_HIP(hipMemcpyAsync(out_first, d_first, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  TRY_HIP(pgpu_ctx_wait(ctx));
+  TRY_HIP(hipGetLastError());
+  const unsigned long long total = out_first[nq];
+  if (n_out) *n_out = (size_t)total;
+  call.elapsed_ms(0, &t_find_ms[0]);
+  // no failure of the stream: it has been waited for, and the caller repeats the call with room for *n_out
+  if (total > out_cap) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "position buffer too small");
+  if (total == 0) return PGPU_OK;
+  TRY_HIP(hipMalloc((void**)&call.d2, (size_t)total * sizeof(uint32_t)));
+  TRY_HIP(call.record(2));
+  hipLaunchKernelGGL(find_fill_kernel, grid, blk, 0, st, ix, d_pats, d_q, d_iv, d_first, (uint32_t*)call.d2);
+  TRY_HIP(call.record(3));
+  TRY_HIP(hipMemcpyAsync(out, call.d2, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  TRY_HIP(pgpu_ctx_wait(ctx));
+  TRY_HIP(hipGetLastError());
+  call.elapsed_ms(1, &t_find_ms[1]);
+  return PGPU_OK;
 }

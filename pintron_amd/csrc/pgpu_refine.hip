@@ -12,6 +12,7 @@
 //                   as the host code has them.
 #include <string.h>
 
+#include "pgpu_query_call.h"
 #include "pgpu_refine_body.h"
 
 namespace {
@@ -37,35 +38,14 @@ void refine_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __r
 
 thread_local double t_refine_ms = 0.0;
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// device buffers and events of one call: freed whichever way the call ends (as pgpu_classify.hip)
-struct CallBuffers {
-  uint8_t* d = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; hipStream_t st; bool failed = false;
-  explicit CallBuffers(hipStream_t s) : st(s) {}
-  ~CallBuffers() {
-    if (failed) (void)hipStreamSynchronize(st);            // nothing of this call may outlive its buffers
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(d);
-  }
-};
-
-bool coordinate_ok(int32_t v, size_t len) { return v >= -1 && (v < 0 || (size_t)v <= len); }
-
 }  // namespace
-
-#define TRY_HIP(call)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (call);                                                                  \
-    if (e_ != hipSuccess) { cb.failed = true;                                                \
-      return pgpu_ctx_fail(ctx, e_ == hipErrorOutOfMemory ? PGPU_ENOMEM : PGPU_EDEVICE, hipGetErrorString(e_)); } \
-  } while (0)
 
 extern "C" double pgpu_index_refine_introns_kernel_ms(void) { return t_refine_ms; }
 
 extern "C" int pgpu_index_refine_introns(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
                                          const char* rows, size_t rows_len,
                                          const pgpu_refine_query* q, size_t n, pgpu_refine_result* out) {
+  t_refine_ms = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
   static_assert(sizeof(pgpu_refine_query) == 96 && sizeof(pgpu_refine_result) == 48 && sizeof(pgpu_factor) == 16, "ABI layout");
   if (!ctx || !idx || (n && (!q || !out)) || (ests_len && !ests) || (rows_len && !rows)) return PGPU_EINVAL;
   if (n > 0x7fffffffull) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 queries in one call");
@@ -75,38 +55,32 @@ extern "C" int pgpu_index_refine_introns(pgpu_ctx* ctx, const pgpu_index* idx, c
     bool ok = x.est_off <= ests_len && x.est_len <= ests_len - x.est_off && x.dim != 0 && x.rows_off <= rows_len &&
               2ull * x.dim <= rows_len - x.rows_off && (x.flags & ~PGPU_REFINE_FIRST_INTRON) == 0 &&
               x.donor.EST_end < x.acceptor.EST_start && x.donor.GEN_end < x.acceptor.GEN_start;
-    for (const pgpu_factor* f : { &x.donor, &x.acceptor })
-      ok = ok && coordinate_ok(f->EST_start, x.est_len) && coordinate_ok(f->EST_end, x.est_len) && coordinate_ok(f->GEN_start, glen) &&
-           coordinate_ok(f->GEN_end, glen);
+    ok = ok && factor_ok(x.donor, x.est_len, glen) && factor_ok(x.acceptor, x.est_len, glen) &&
+         suffpref_ok(x.suffpref_length_on_est, x.suffpref_length_for_intron, x.suffpref_length_on_gen);
     for (int32_t v : { x.factor_cut, x.intron_start, x.intron_end, x.intron_start_on_align, x.intron_end_on_align })
       ok = ok && v >= 0 && (uint32_t)v <= x.dim;
-    for (int32_t v : { x.suffpref_length_on_est, x.suffpref_length_for_intron, x.suffpref_length_on_gen })
-      ok = ok && v >= 0 && v <= (1 << 24);
     if (!ok)
       return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad refine query (an offset past its buffer, an unknown flag, dim == 0, a donor that is "
                                              "not in front of the acceptor, or a coordinate outside what it indexes)");
   }
-  t_refine_ms = 0.0;
   if (n == 0) return PGPU_OK;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
-  hipStream_t st = pgpu_ctx_stream(ctx);
-  CallBuffers cb(st);
-  pgpu_range_push("refine_introns");
-  struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
+  QueryCall call(ctx, "refine_introns");
+  const hipStream_t st = call.st;
   const size_t o_rows = up256(ests_len + 64), o_q = o_rows + up256(rows_len + 64), o_r = o_q + up256(n * sizeof(pgpu_refine_query)),
                total = o_r + up256(n * sizeof(pgpu_refine_result));
-  TRY_HIP(hipMalloc((void**)&cb.d, total));
-  if (pgpu_ctx_timing(ctx)) for (auto& e : cb.ev) TRY_HIP(hipEventCreate(&e));
-  if (ests_len) TRY_HIP(hipMemcpyAsync(cb.d, ests, ests_len, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(cb.d + o_rows, rows, rows_len, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(cb.d + o_q, q, n * sizeof(pgpu_refine_query), hipMemcpyHostToDevice, st));
-  if (cb.ev[0]) TRY_HIP(hipEventRecord(cb.ev[0], st));
-  hipLaunchKernelGGL(refine_kernel, dim3((unsigned)n), dim3(64), 0, st, pgpu_index_genomic(idx), (uint32_t)glen, cb.d, cb.d + o_rows,
-                     (const pgpu_refine_query*)(cb.d + o_q), (pgpu_refine_result*)(cb.d + o_r));
-  if (cb.ev[1]) TRY_HIP(hipEventRecord(cb.ev[1], st));
-  TRY_HIP(hipMemcpyAsync(out, cb.d + o_r, n * sizeof(pgpu_refine_result), hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMalloc((void**)&call.d, total));
+  TRY_HIP(call.timing_events(1));
+  if (ests_len) TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_rows, rows, rows_len, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof(pgpu_refine_query), hipMemcpyHostToDevice, st));
+  TRY_HIP(call.record(0));
+  hipLaunchKernelGGL(refine_kernel, dim3((unsigned)n), dim3(64), 0, st, pgpu_index_genomic(idx), (uint32_t)glen, call.d, call.d + o_rows,
+                     (const pgpu_refine_query*)(call.d + o_q), (pgpu_refine_result*)(call.d + o_r));
+  TRY_HIP(call.record(1));
+  TRY_HIP(hipMemcpyAsync(out, call.d + o_r, n * sizeof(pgpu_refine_result), hipMemcpyDeviceToHost, st));
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
-  if (cb.ev[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, cb.ev[0], cb.ev[1]); t_refine_ms = ms; }
+  call.elapsed_ms(0, &t_refine_ms);
   return PGPU_OK;
 }

@@ -5,12 +5,11 @@ bound; the CPU restatement of the classification (tests/small_exon_lib.py) equal
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import resource_lib
 import small_exon_lib as SL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,29 +73,9 @@ def test_null_arguments_are_einval_without_a_device(capi):
     assert L.pgpu_index_small_exons(None, None, b"ACGTAC", 6, q, 1, r) == capi.PGPU_EINVAL
 
 
-def _hipcc():
-    for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
 def test_kernels_have_no_stack_frame_and_little_lds(tmp_path):
-    hipcc = _hipcc()
-    assert hipcc, "no hipcc here"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "pgpu_classify.hip", "-o",
-                        str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", ln)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    assert resource_lib.hipcc(), "no hipcc here"
+    usage = resource_lib.usage("pgpu_classify.hip", tmp_path)
     kernels = {k: v for k, v in usage.items() if "kernel" in k}
     for want in ("class_tables_kernel", "classify_kernel", "small_exons_kernel"):
         assert any(want in k for k in kernels), (want, sorted(usage))

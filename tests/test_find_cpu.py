@@ -3,13 +3,12 @@ fallback, and its kernels use no scratch memory and spill no register (hipcc cro
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+from resource_lib import usage as _usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pintron_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -49,33 +48,6 @@ def test_find_has_no_cpu_fallback(capi):
     with pytest.raises(capi.PgpuError) as e:
         capi.Context(0)                                   # no context, no index, no query
     assert e.value.code == capi.PGPU_EDEVICE
-
-
-def _hipcc():
-    for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
-def _usage(source, tmp_path):
-    hipcc = _hipcc()
-    if not hipcc:
-        pytest.skip("no hipcc here")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", source, "-o",
-                        str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", ln)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
 
 
 def test_find_kernels_have_no_stack_frame(tmp_path):

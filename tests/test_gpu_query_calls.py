@@ -1,0 +1,225 @@
+"""GPU: what the host side of every query on the resident index promises around its kernels
+(pintron_amd/csrc/pgpu_query_call.h), entry by entry on one sequence of 700 bases with two or three queries each:
+the millisecond slot is set with timing on and 0.0 without it, with the same answers; a call refused with PGPU_EINVAL
+resets the slot and leaves its message; the context answers the same afterwards; an empty call is PGPU_OK with the slot
+at 0.  For pgpu_index_find also the PGPU_ENOSPC round and a second context on the same index.  The answers are held
+against the CPU restatements (bytes.find, tests/small_exon_lib.py, tests/refine_lib.py, tests/chain_lib.py), never
+against the library alone; the messages are the literal texts of the source."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import chain_lib as CL
+import refine_lib as RL
+import small_exon_lib as SL
+
+pytestmark = pytest.mark.gpu
+
+MESSAGES = {
+    "find": "bad find query (reserved != 0, lo > hi, or the pattern leaves the pattern buffer)",
+    "small_exons": "bad small-exon query (reserved != 0, min_intron_len < 4, or efact / allgfact leave their sequence)",
+    "refine_introns": "bad refine query (an offset past its buffer, an unknown flag, dim == 0, a donor that is not in front of "
+                      "the acceptor, or a coordinate outside what it indexes)",
+    "refine_chains": "bad chain query (a range past its buffer, reserved != 0, no exon, an exon two chains share, a donor that "
+                     "is not in front of its acceptor, or a coordinate outside what it indexes)",
+}
+
+
+def occurrences(gen, pat, lo, hi):
+    hi = min(hi, len(gen))
+    out, t = [], gen.find(pat, lo, hi)
+    while t >= 0:
+        out.append(t)
+        t = gen.find(pat, t + 1, hi)
+    return out
+
+
+def find_on(ctx, idx, blob, queries, n, out):
+    """pgpu_index_find on any context that shares the index -> (rc, first, n_out)"""
+    first = np.full(n + 1, 7, dtype=np.uint64)
+    total = C.c_size_t(99)
+    rc = ctx.L.pgpu_index_find(ctx.h, idx.h, blob, len(blob), queries, n, out.ctypes.data_as(C.POINTER(C.c_uint32)), len(out),
+                               first.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total))
+    return rc, first, total.value
+
+
+class Entry:
+    """one entry on the shared index: good() -> (rc, answer as bytes), bad() and empty() -> rc, ms() -> the slots"""
+
+
+@pytest.fixture(scope="module")
+def world(O):
+    import pintron_amd.capi as capi
+    rng = np.random.default_rng(12)
+    g = bytearray(RL.rnd(rng, 700))
+    made = None
+    while made is None or made[4] >= 370:              # one chain of two exons in the first half of the sequence
+        if made is not None:
+            for p, s in reversed(saved):
+                g[p:p + len(s)] = s
+        before = bytes(g)
+        made = CL.make_chain(rng, g, 40, 2, aims=[None])
+        if made is not None:
+            saved = [(p, before[p:p + len(s)]) for p, s in made[3]]
+    est, exons, st = made[:3]
+    e1, s0, sl, e2 = 410, 530, 12, 652                  # exon1 GT..AG small exon GT..AG exon2 behind it
+    g[e1:e1 + 2], g[s0 - 2:s0], g[s0 + sl:s0 + sl + 2], g[e2 - 2:e2] = b"GT", b"AG", b"GT", b"AG"
+    gen = bytes(g)
+    ctx = capi.Context(0)                               # its own: the timing switch is turned here
+    idx = capi.Index(ctx, gen)
+    entries = {}
+
+    # find: three patterns cut from the sequence, in the whole of it and in a window
+    pats = [gen[100:106], gen[300:304], b"GT"]
+    wins = [(0, 700), (250, 400), (0, 9999)]
+    want_pos = [occurrences(gen, p, lo, hi) for p, (lo, hi) in zip(pats, wins)]
+    assert all(want_pos) and sum(len(w) for w in want_pos) > 3
+    blob = b"".join(pats)
+
+    def find_queries(reserved=0):
+        q, off = (capi.FindQuery * len(pats))(), 0
+        for i, (p, (lo, hi)) in enumerate(zip(pats, wins)):
+            q[i] = capi.FindQuery(off, len(p), reserved if i == 1 else 0, lo, hi)
+            off += len(p)
+        return q
+    total_want, fq = sum(len(w) for w in want_pos), find_queries()
+
+    def find_good():
+        out = np.zeros(total_want, dtype=np.uint32)
+        rc, first, total = find_on(ctx, idx, blob, fq, len(pats), out)
+        return rc, first.tobytes() + out.tobytes()
+    want_first = np.cumsum([0] + [len(w) for w in want_pos]).astype(np.uint64)
+    e = entries["find"] = Entry()
+    e.total, e.blob, e.queries, e.want_pos = total_want, blob, fq, want_pos
+    e.good = find_good
+    e.want = want_first.tobytes() + np.array(sum(want_pos, []), dtype=np.uint32).tobytes()
+    e.bad = lambda: find_on(ctx, idx, blob, find_queries(reserved=1), len(pats), np.zeros(total_want, dtype=np.uint32))[0]
+    e.empty = lambda: find_on(ctx, idx, blob, fq, 0, np.zeros(total_want, dtype=np.uint32))[0]
+    e.ms = lambda: tuple(idx.find_kernel_ms().values())
+
+    # small exons: the planted one with and without borders, and a factor cut anywhere
+    rows = [(gen[e1 - a:e1] + gen[s0:s0 + sl] + gen[e2:e2 + b], e1 - a, e2 + b - (e1 - a), a + 6, b + 6, 40) for a, b in ((4, 3), (0, 0))]
+    rows.append((gen[450:470], 380, 300, 8, 8, 4))
+    sq = np.zeros(len(rows), dtype=np.dtype(SL.QUERY_DTYPE))
+    off = 0
+    for i, (ef, gs, gl, f1, f2, mil) in enumerate(rows):
+        sq[i] = (off, len(ef), gs, gl, f1, f2, mil, 0, 0)
+        off += len(ef)
+    sests = b"".join(r[0] for r in rows)
+    want_se = SL.transcribe(gen, sests, sq, SL.reference_classify(gen))
+    sres = np.zeros(len(rows), dtype=np.dtype(capi.SEXON_RESULT_DTYPE))
+    for i, w in enumerate(want_se):
+        for f, v in zip(("len", "offstart", "offend", "gpos", "i1type", "i2type"), w):
+            sres[i][f] = v
+    sbad = sq.copy()
+    sbad["min_intron_len"][1] = 3
+    e = entries["small_exons"] = Entry()
+    e.good = lambda: (lambda rc, res: (rc, res.tobytes()))(*idx.small_exons_raw(sests, sq, len(sq)))
+    e.want = sres.tobytes()
+    e.bad = lambda: idx.small_exons_raw(sests, sbad, len(sbad))[0]
+    e.empty = lambda: idx.small_exons_raw(sests, sq, 0)[0]
+    e.ms = lambda: (idx.small_exons_kernel_ms(),)
+
+    # refine_introns: the chain's intron as the first and as a later one, rows from the oracle's CPU gap alignment
+    er, gr, v = RL.oracle_rows(O, est, gen, exons[0], exons[1], *st[:3])
+    items = [(est, er, gr, v, exons[0], exons[1], first, st) for first in (True, False)]
+    rests, rrows, rq = RL.query_array(items)
+    want_r = [RL.refine(est, gen, er, gr, v, exons[0], exons[1], first, *st) for first in (True, False)]
+    assert all(w[0] == RL.OK for w in want_r)
+    rres = np.zeros(len(items), dtype=np.dtype(capi.REFINE_RESULT_DTYPE))
+    for i, (status, refined, path, d, a) in enumerate(want_r):
+        rres[i] = (status, refined, path, 0, d, a)
+    rbad = rq.copy()
+    rbad["dim"][1] = 0
+    e = entries["refine_introns"] = Entry()
+    e.good = lambda: (lambda rc, res: (rc, res.tobytes()))(*idx.refine_introns_raw(rests, rrows, rq, len(rq)))
+    e.want = rres.tobytes()
+    e.bad = lambda: idx.refine_introns_raw(rests, rrows, rbad, len(rbad))[0]
+    e.empty = lambda: idx.refine_introns_raw(rests, rrows, rq, 0)[0]
+    e.ms = lambda: (idx.refine_introns_kernel_ms(),)
+
+    # refine_chains: the chain under its settings and with min_intron_length 4
+    batch = [(est, exons, st), (est, exons, st[:3] + (4,))]
+    cests, cexons, cq = CL.batch_arrays(batch)
+    want_c = [CL.chain(x, gen, ex, s) for x, ex, s in batch]
+    assert all(w[0] == CL.OK for w in want_c)
+    oex, ost = cexons.copy(), np.zeros(len(cexons), dtype=np.uint8)
+    cres = np.zeros(len(batch), dtype=np.dtype(capi.CHAIN_RESULT_DTYPE))
+    k = 0
+    for i, (status, done, dropped, ex2, steps) in enumerate(want_c):
+        cres[i] = (status, done, dropped, 0)
+        for x, s in zip(ex2, steps):
+            oex[k], ost[k] = tuple(x), s
+            k += 1
+    cbad = cq.copy()
+    cbad["reserved"][1] = 1
+
+    def chains(q, n):
+        rc, a, b, c = idx.refine_chains_raw(cests, cexons, q, n)
+        return rc, a.tobytes() + b.tobytes() + c.tobytes()
+    e = entries["refine_chains"] = Entry()
+    e.good = lambda: chains(cq, len(cq))
+    e.want = oex.tobytes() + ost.tobytes() + cres.tobytes()
+    e.bad = lambda: chains(cbad, len(cbad))[0]
+    e.empty = lambda: chains(cq, 0)[0]
+    e.empty_answer = cexons.tobytes() + bytes(len(cexons))          # n == 0: the exons copied, the steps zeroed
+    e.chains = chains
+    e.cq = cq
+    e.ms = lambda: (idx.refine_chains_kernel_ms(),)
+
+    yield capi, ctx, idx, gen, entries
+    idx.close()
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", ["find", "small_exons", "refine_introns", "refine_chains"])
+def test_the_contract_of_a_timed_entry(world, name):
+    capi, ctx, idx, gen, entries = world
+    e = entries[name]
+    rc, timed = e.good()
+    assert rc == capi.PGPU_OK and timed == e.want                # the CPU restatement's answer
+    assert all(ms > 0.0 for ms in e.ms()), e.ms()
+    ctx.L.pgpu_set_timing(ctx.h, 0)
+    try:
+        rc, untimed = e.good()
+        assert rc == capi.PGPU_OK and all(ms == 0.0 for ms in e.ms()), e.ms()
+        assert untimed == timed
+    finally:
+        ctx.L.pgpu_set_timing(ctx.h, 1)
+    assert e.good()[0] == capi.PGPU_OK and all(ms > 0.0 for ms in e.ms())     # a slot the refusal has to reset
+    assert e.bad() == capi.PGPU_EINVAL
+    assert all(ms == 0.0 for ms in e.ms()), e.ms()
+    assert ctx.L.pgpu_last_error(ctx.h).decode() == MESSAGES[name]
+    rc, again = e.good()
+    assert rc == capi.PGPU_OK and again == timed and all(ms > 0.0 for ms in e.ms())
+    assert e.empty() == capi.PGPU_OK
+    assert all(ms == 0.0 for ms in e.ms()), e.ms()
+
+
+def test_an_empty_chain_call_copies_the_exons(world):
+    capi, ctx, idx, gen, entries = world
+    e = entries["refine_chains"]
+    rc, answer = e.chains(e.cq, 0)
+    assert rc == capi.PGPU_OK and answer == e.empty_answer
+
+
+def test_find_without_room_then_with_it_then_on_a_second_context(world):
+    capi, ctx, idx, gen, entries = world
+    e = entries["find"]
+    n, flat = len(e.want_pos), sum(e.want_pos, [])
+    short = np.full(e.total - 1, 0xDEADBEEF, dtype=np.uint32)
+    rc, first, total = find_on(ctx, idx, e.blob, e.queries, n, short)
+    assert rc == capi.PGPU_ENOSPC and total == e.total and int(first[n]) == e.total
+    assert ctx.L.pgpu_last_error(ctx.h).decode() == "position buffer too small"
+    assert (short == 0xDEADBEEF).all()
+    ms = idx.find_kernel_ms()
+    assert ms["count+scan"] > 0.0 and ms["fill"] == 0.0          # the first phase ran and was timed, the second did not run
+    out = np.zeros(e.total, dtype=np.uint32)
+    rc, first, total = find_on(ctx, idx, e.blob, e.queries, n, out)
+    assert rc == capi.PGPU_OK and total == e.total and out.tolist() == flat
+    assert all(v > 0.0 for v in idx.find_kernel_ms().values())
+    with capi.Context(0) as other:
+        out2 = np.zeros(e.total, dtype=np.uint32)
+        rc, first2, total2 = find_on(other, idx, e.blob, e.queries, n, out2)
+        assert rc == capi.PGPU_OK and total2 == e.total and out2.tolist() == flat and np.array_equal(first2, first)

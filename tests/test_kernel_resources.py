@@ -5,42 +5,7 @@ call: the call gave the kernel a stack frame (96 B of scratch per lane) and ever
 routine ran or not.  Nothing in the parity tests can see that, and the profile that did was
 taken by chance -- so the resource usage the compiler reports is pinned here: no scratch, no spilled vector
 registers, at most 128 VGPRs (four waves per SIMD), and the LDS budget that lets four workgroups share a CU."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pintron_amd", "csrc")
-
-
-def _hipcc():
-    for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
-        if c and os.path.exists(c):
-            return c
-    return None
-
-
-def _usage(source, tmp_path):
-    hipcc = _hipcc()
-    if not hipcc:
-        pytest.skip("no hipcc here")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", source, "-o",
-                        str(tmp_path / "k.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for ln in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", ln)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return out
+from resource_lib import usage as _usage
 
 
 def test_dp_kernels_have_no_stack_frame(tmp_path):
