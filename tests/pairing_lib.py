@@ -39,6 +39,8 @@ class OracleIndex:
         L.orc_index_destroy.argtypes = [C.c_void_p]
         L.orc_index_sa.restype = C.POINTER(C.c_uint32)
         L.orc_index_sa.argtypes = [C.c_void_p]
+        L.orc_index_lcp.restype = C.POINTER(C.c_uint32)
+        L.orc_index_lcp.argtypes = [C.c_void_p]
         L.orc_pairings.restype = C.c_long
         L.orc_pairings.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_double,
                                    C.c_void_p, C.c_long, C.c_void_p]
@@ -48,6 +50,10 @@ class OracleIndex:
 
     def sa(self):
         return np.ctypeslib.as_array(self.L.orc_index_sa(self.h), shape=(self.n,)).copy()
+
+    def lcp(self):
+        """n + 1 entries: lcp[k] = LCP of the suffixes in slots k - 1 and k, lcp[0] = lcp[n] = 0 (Kasai)"""
+        return np.ctypeslib.as_array(self.L.orc_index_lcp(self.h), shape=(self.n + 1,)).copy()
 
     def pairings(self, est: bytes, min_factor_len=15, rate=0.2):
         n = self.L.orc_pairings(self.h, est, len(est), min_factor_len, rate, self.buf.ctypes.data,
