@@ -304,6 +304,77 @@ int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* e
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_refine_chains_kernel_ms(void);
 
+/* A candidate factorization's cleaning steps, chained: what get_EST_factorizations (src/est-factorizations.c:212-244) does
+ * to one candidate before refine_intron sees it -- check_for_not_source_sink_factorization, check_exon_start_end,
+ * handle_endpoints, clean_external_exons, clean_low_complexity_exons_2, clean_noisy_exons and check_est_coverage -- with
+ * the two end-exon alignments, their trimming, the dust scores and the banded edit distances done on the device for one
+ * step after the other.  One query = one candidate; the call is synchronous and batched like pgpu_index_refine_chains.
+ * add_if_not_exists compares candidates with each other and stays with the caller. */
+#define PGPU_CLEAN_MAX_EXONS      64    /* exons of one factorization; beyond: PGPU_ERANGE for that query   */
+#define PGPU_CLEAN_MAX_END_EXON 4096    /* bytes of an end exon on the EST and on the genomic sequence      */
+typedef struct {
+  uint64_t est_off; uint32_t est_len;   /* EST_seq = ests + est_off, est_len bytes, 1 .. 2^31 - 1           */
+  uint32_t first_exon, n_exons;         /* the candidate = exons[first_exon .. first_exon + n_exons)        */
+  uint32_t reserved;                    /* 0 */
+  double   complexity_threshold;        /* config->complexity_threshold */
+} pgpu_clean_query;                     /* 32 bytes: 0, 8, 12, 16, 20, 24; no padding */
+typedef struct {
+  int32_t  status;                      /* PGPU_OK or PGPU_ERANGE */
+  uint32_t verdict;                     /* 0 kept; the step that rejected: 1 source-sink, 2 start/end order, 3 emptied by
+                                           handle_endpoints, 4 by clean_external_exons, 5 by clean_low_complexity_exons_2,
+                                           6 by clean_noisy_exons, 7 check_est_coverage */
+  uint32_t first_kept, n_kept;          /* the list as it stood when the verdict fell (verdicts 0 and 7), as indices into
+                                           the query's exons; 0, 0 otherwise */
+} pgpu_clean_result;                    /* 16 bytes */
+
+/*  - out_exons (n_exons_total entries) and out_marks (n_exons_total bytes) are parallel to exons: same indices; exons no
+ *    query names are copied, with mark 0.  Only the first EST_start / GEN_start and the last EST_end / GEN_end of the run
+ *    [first_kept, first_kept + n_kept) of a query with verdict 0 or 7 can differ from the input; every other exon is a copy.
+ *    out_marks: bit 0 dropped by handle_endpoints, bit 1 dropped by clean_external_exons, bit 2 dust(genomic) > threshold,
+ *    bit 3 dust(EST) > threshold, bit 4 the K-band verdict was false.  A step that never ran leaves its bits 0.
+ *  - The steps, in order, each on the list as the one before left it (lines of src/est-factorizations.c):
+ *    1. :2111-2125 (one exon whose EST_start lies outside [0, est_len): verdict 1), then :1989-2019 (an exon with
+ *       start > end on either string, or a start in front of the end of the exon before it: verdict 2).
+ *    2. handle_endpoints (:2127-2301).  Each alignment is PGPU_DP_ALIGN's, bit for bit: a = the exon on the EST, b = the
+ *       exon on the genomic sequence, N a wildcard.  The head is walked from the left until "more than 5 matches", tested
+ *       one column late: an alignment of exactly six matching columns drops the exon, seven keep it; the exon then begins
+ *       where that run of matches begins.  The tail likewise from the right with "more than 10", and it ends where that
+ *       run ends; its gap-closing loop (:2241-2281) then rewrites the rows as it goes, and a byte behind a row reads 0.  The
+ *       tail is dropped only when its new GEN_end lies in front of its GEN_start: a walk that reaches the first column
+ *       without stopping keeps a tail whose first column matches (eleven matching columns and nothing else: kept whole)
+ *       and drops one whose first column does not (that column, then ten matches: dropped; then eleven: kept).  With one
+ *       exon the tail step aligns the head as already trimmed.
+ *    3. clean_external_exons (:1706-1825): an end exon shorter than 10 on the genomic sequence is dropped; one shorter than
+ *       20 stays only with its splice sites (G, then T or C behind the head and behind the exon before the tail; A, G in
+ *       front of the tail and of the exon behind the head; compared case-insensitively, a genomic byte outside the
+ *       sequence reads as 0, and an exon without that neighbour is dropped) and an edit distance of 0 between its two
+ *       strings.  The distance is only tested `> 0`, which is exactly "the two real_substring pieces differ as byte
+ *       strings", no wildcard: no DP is run for it.
+ *    4. clean_low_complexity_exons_2 (:1667-1704): PGPU_DP_KBAND's `tail = 1` dust flags for every exon, then
+ *       update_with_subfact_with_best_coverage (:1900-1987) over the flagged ones: the run of unflagged exons with the
+ *       largest EST_end - EST_start + 1 stays; a strictly larger cover wins, so the first of equals does.
+ *    5. clean_noisy_exons (:1842-1898) with only_internals = false: the bound of :1828-1839 in FP64 from the genomic length,
+ *       K_band_edit_distance as PGPU_DP_KBAND has it, early exits included; then the same best-run rule.
+ *    6. check_est_coverage (:2303-2321): (double) cover / (double) est_len >= (double) 0.35f, else verdict 7.
+ *  - Caps refuse only the query that reaches them: its result is PGPU_ERANGE with verdict, first_kept and n_kept 0, its exons
+ *    are copied unchanged and their marks are 0.  More than PGPU_CLEAN_MAX_EXONS exons (tested before step 1); an end exon,
+ *    as it is when it is aligned, longer than PGPU_CLEAN_MAX_END_EXON on either string; an end-exon alignment the plan
+ *    builder would send neither to lev_wave<ALIGN> (at most 64 EST bytes) nor to an align_band job settled inside the band
+ *    (65 .. 4096 EST bytes, lengths within 31 of each other, score <= 31); an exon in the list at step 5 whose bound exceeds
+ *    31, i.e. a genomic length above 1 033.  A query an earlier step rejects never reaches a later cap.
+ *  - PGPU_EINVAL for the whole call: a null pointer (no message); n_exons == 0; first_exon + n_exons > n_exons_total or
+ *    est_off + est_len > ests_len; est_len == 0 or > 2^31 - 1; reserved != 0; two queries share an exon; a factor coordinate
+ *    outside what pgpu_index_refine_introns accepts; for a query that passes the two checks of step 1 (whatever its number of
+ *    exons): a first exon with EST_start < 0 or GEN_start < 0, or a last exon with EST_end >= est_len or GEN_end >= the length of
+ *    the sequence (the my_asserts of :2140-2141 and :2199-2200, which the reference's build compiles out).
+ *  - n == 0 is PGPU_OK (out_exons = exons, out_marks = 0).  idx may be built or loaded. */
+int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                            const pgpu_factor* exons, size_t n_exons_total, const pgpu_clean_query* q, size_t n,
+                            pgpu_factor* out_exons, uint8_t* out_marks, pgpu_clean_result* out);
+/* HIP-event time of the kernel of the calling thread's last pgpu_index_clean_chains on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_clean_chains_kernel_ms(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */

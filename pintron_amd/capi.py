@@ -84,6 +84,15 @@ class ChainResult(C.Structure):    # pgpu_chain_result
     _fields_ = [("status", C.c_int32), ("done", C.c_uint32), ("dropped_first", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class CleanQuery(C.Structure):     # pgpu_clean_query
+    _fields_ = [("est_off", C.c_uint64), ("est_len", C.c_uint32), ("first_exon", C.c_uint32), ("n_exons", C.c_uint32),
+                ("reserved", C.c_uint32), ("complexity_threshold", C.c_double)]
+
+
+class CleanResult(C.Structure):    # pgpu_clean_result
+    _fields_ = [("status", C.c_int32), ("verdict", C.c_uint32), ("first_kept", C.c_uint32), ("n_kept", C.c_uint32)]
+
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -100,6 +109,10 @@ CHAIN_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_exon", "<u4
                      ("min_intron_length", "<i4")]
 CHAIN_RESULT_DTYPE = [("status", "<i4"), ("done", "<u4"), ("dropped_first", "<u4"), ("pad", "<u4")]
 FACTOR_DTYPE = _FACTOR_DTYPE
+CLEAN_MAX_EXONS, CLEAN_MAX_END_EXON = 64, 4096
+CLEAN_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u4"), ("reserved", "<u4"),
+                     ("complexity_threshold", "<f8")]
+CLEAN_RESULT_DTYPE = [("status", "<i4"), ("verdict", "<u4"), ("first_kept", "<u4"), ("n_kept", "<u4")]
 
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
@@ -111,6 +124,7 @@ assert C.sizeof(DpJob) == 48 and C.sizeof(DpResult) == 48 and C.sizeof(FindQuery
 assert C.sizeof(Intron) == 8 and C.sizeof(SexonQuery) == 40 and C.sizeof(SexonResult) == 32
 assert C.sizeof(Factor) == 16 and C.sizeof(RefineQuery) == 96 and C.sizeof(RefineResult) == 48
 assert C.sizeof(ChainQuery) == 40 and C.sizeof(ChainResult) == 16
+assert C.sizeof(CleanQuery) == 32 and C.sizeof(CleanResult) == 16
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -120,6 +134,7 @@ EXPORTS = [
     "pgpu_index_classify", "pgpu_index_score5", "pgpu_index_small_exons", "pgpu_index_small_exons_kernel_ms",
     "pgpu_index_refine_introns", "pgpu_index_refine_introns_kernel_ms",
     "pgpu_index_refine_chains", "pgpu_index_refine_chains_kernel_ms",
+    "pgpu_index_clean_chains", "pgpu_index_clean_chains_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -184,6 +199,10 @@ def lib():
                                                C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(ChainResult)]
         L.pgpu_index_refine_chains_kernel_ms.argtypes = []
         L.pgpu_index_refine_chains_kernel_ms.restype = C.c_double
+        L.pgpu_index_clean_chains.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(CleanQuery), sz,
+                                              C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(CleanResult)]
+        L.pgpu_index_clean_chains_kernel_ms.argtypes = []
+        L.pgpu_index_clean_chains_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -419,6 +438,31 @@ class Index:
 
     def refine_chains_kernel_ms(self):
         return self.ctx.L.pgpu_index_refine_chains_kernel_ms()
+
+    def clean_chains_raw(self, ests: bytes, exons, queries, n: int):
+        """One pgpu_index_clean_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+        CLEAN_QUERY_DTYPE.  Returns (rc, out_exons, out_marks, results as a numpy array of CLEAN_RESULT_DTYPE)."""
+        import numpy as np
+        out_exons = np.zeros(len(exons), dtype=np.dtype(FACTOR_DTYPE))
+        out_marks = np.zeros(len(exons), dtype=np.uint8)
+        res = np.zeros(n, dtype=np.dtype(CLEAN_RESULT_DTYPE))
+        rc = self.ctx.L.pgpu_index_clean_chains(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)),
+                                                len(exons), queries.ctypes.data_as(C.POINTER(CleanQuery)), n,
+                                                out_exons.ctypes.data_as(C.POINTER(Factor)),
+                                                out_marks.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                res.ctypes.data_as(C.POINTER(CleanResult)))
+        return rc, out_exons, out_marks, res
+
+    def clean_chains(self, ests: bytes, exons, queries):
+        """The reference's cleaning steps over every candidate factorization `queries` names (end-exon alignments and
+        trimming, external exons, dust, banded edit distances, coverage, chained on the device): (out_exons, out_marks,
+        results) as numpy arrays."""
+        rc, out_exons, out_marks, res = self.clean_chains_raw(ests, exons, queries, len(queries))
+        self.ctx.check(rc)
+        return out_exons, out_marks, res
+
+    def clean_chains_kernel_ms(self):
+        return self.ctx.L.pgpu_index_clean_chains_kernel_ms()
 
     def close(self):
         if self.h:

@@ -1,0 +1,417 @@
+// A candidate factorization's cleaning steps, chained, on the resident index.  Semantics: include/pintron_gpu.h
+// (pgpu_index_clean_chains): one query is one candidate of get_EST_factorizations (src/est-factorizations.c:212-244), and
+// the answer is the verdict of the six steps with the list as they left it.
+//
+//   clean_kernel    one wave per query; a wave that has finished a query takes the next one of its stride.  The exons sit
+//                   in the wave's LDS, one lane loads one; the list is always a run [lo, hi) of them (the steps only drop
+//                   at the ends or keep one run), the flagged exons of steps 4 and 5 are a 64-bit ballot, and the best-run
+//                   rule is a scan over its set bits.  Without the host in between:
+//                     endpoints  lev_wave_body<1, ALIGN> + align_traceback_wave, or align_band_sweep + align_band_traceback,
+//                                of pgpu_wave_dp.h on a DevJob built here -- the code and the choice of the PGPU_DP_ALIGN
+//                                jobs of a plan -- then head_walk_window / tail_walk_window / close_tail_gaps over the two
+//                                gapped rows, 64 columns at a time: the walks of endpoint_epilogue, here over every window;
+//                     external   lengths, splice-site bytes and a byte comparison: no DP;
+//                     dust       dust_flags_wave per exon;
+//                     noisy      lev_wave_body<1, KBAND> per exon (kband_band_sweep, or the whole matrix of a short exon).
+//                   Divergence is per query: everything that decides is uniform over the wave.
+//                   The direction words and the two gapped rows live in a per-wave workspace in HBM inside the call's one
+//                   allocation, sized by the host for the longest end exon of the call; the traceback's window is in LDS
+//                   (DESIGN.md section 5g).
+#include <stdlib.h>
+#include <string.h>
+
+#include "pgpu_internal.h"
+#include "pgpu_query_call.h"
+#include "pgpu_wave_dp.h"
+
+namespace {
+
+constexpr uint32_t MAX_EXONS = PGPU_CLEAN_MAX_EXONS;
+constexpr uint32_t MAX_END = PGPU_CLEAN_MAX_END_EXON;
+constexpr uint32_t MAX_KBAND = 31;                     // 2k + 1 <= 64 diagonals on the lanes (kband_band_sweep)
+static_assert(MAX_EXONS == 64, "one lane per exon, one ballot bit per exon");
+static_assert(ALIGN_BAND_K == MAX_KBAND, "both bands take the whole wave");
+
+// direction bytes of one end-exon alignment, as the plan builder sizes them: lev_wave<ALIGN> [step][64 lanes] of 1 B,
+// align_band [row / 16][64 lanes] of 4 B
+__host__ __device__ inline size_t dirs_wave(uint32_t lb) { return ((size_t)lb + 64) * 64; }
+__host__ __device__ inline size_t dirs_band(uint32_t la) { return ((size_t)(la >> 4) + 1) * 256; }
+__host__ __device__ inline size_t rows_bytes(uint32_t la, uint32_t lb) { return (2 * ((size_t)la + lb + 1) + 15) & ~(size_t)15; }
+
+struct CleanLds {
+  __attribute__((aligned(16))) uint8_t win[TB_WIN_BYTES];   // the traceback's direction window ...
+  uint8_t path[TB_PATH];                                    // ... and path
+  pgpu_factor ex[MAX_EXONS];                                // the query's exons as the steps leave them
+  uint8_t marks[MAX_EXONS];
+};
+
+// the two gapped rows in the wave's workspace (a 0 follows each row)
+struct MemRows {
+  uint8_t* ea; uint8_t* ga;
+  __device__ __forceinline__ uint32_t e(uint32_t q) const { return ea[q]; }
+  __device__ __forceinline__ uint32_t g(uint32_t q) const { return ga[q]; }
+  __device__ __forceinline__ void set_e(uint32_t q, uint32_t v) { ea[q] = (uint8_t)v; }
+  __device__ __forceinline__ void set_g(uint32_t q, uint32_t v) { ga[q] = (uint8_t)v; }
+};
+
+// update_with_subfact_with_best_coverage (:1900-1987) on the run [lo, hi) with the exons of `bad` flagged: the run of
+// unflagged exons with the largest cover on the EST, the first of equals; lo == hi when none is left
+__device__ __forceinline__ void best_run(const pgpu_factor* ex, unsigned long long bad, uint32_t& lo, uint32_t& hi) {
+  if (!bad) return;
+  int best_cover = -1;
+  uint32_t best_lo = 0, best_hi = 0, left = lo;
+  while (bad) {
+    const uint32_t r = (uint32_t)__builtin_ctzll(bad);
+    bad &= bad - 1ull;
+    if (left < r) {
+      const int cover = ex[r - 1].EST_end - ex[left].EST_start + 1;
+      if (cover > best_cover) { best_cover = cover; best_lo = left; best_hi = r; }
+    }
+    left = r + 1;
+  }
+  if (left < hi) {
+    const int cover = ex[hi - 1].EST_end - ex[left].EST_start + 1;
+    if (cover > best_cover) { best_cover = cover; best_lo = left; best_hi = hi; }
+  }
+  lo = best_lo; hi = best_hi;
+}
+
+__global__ __launch_bounds__(64)
+void clean_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __restrict__ ests, const pgpu_factor* __restrict__ exons,
+                  const pgpu_clean_query* __restrict__ queries, uint32_t n_queries, uint8_t* __restrict__ ws,
+                  const size_t ws_dirs, const size_t ws_rows, pgpu_factor* __restrict__ out_exons, uint8_t* __restrict__ out_marks,
+                  pgpu_clean_result* __restrict__ out, uint32_t* __restrict__ undersized) {
+  __shared__ CleanLds S;
+  const uint32_t lane = threadIdx.x;
+  const size_t ws_wave = (ws_dirs + ws_rows + sizeof(DevResult) + 255) & ~(size_t)255;
+  uint8_t* const w = ws + (size_t)blockIdx.x * ws_wave;
+  DevResult* const res = reinterpret_cast<DevResult*>(w + ws_dirs + ws_rows);
+  // a genomic byte for the splice sites: upper case, 0 outside the sequence
+  auto site = [&](int i) -> uint32_t { return (i >= 0 && (uint32_t)i < n) ? ((uint32_t)T[i] & ~32u) : 0u; };
+  for (uint32_t c = blockIdx.x; c < n_queries; c += gridDim.x) {
+    const pgpu_clean_query q = queries[c];
+    const uint8_t* const est = ests + q.est_off;
+    const uint32_t ne = q.n_exons;
+    pgpu_clean_result cr;
+    cr.status = PGPU_OK; cr.verdict = 0; cr.first_kept = 0; cr.n_kept = 0;
+    uint32_t lo = 0, hi = ne;
+    bool refused = ne > MAX_EXONS;
+    __syncthreads();                                           // the query before is done with the LDS
+    if (!refused && lane < ne) { S.ex[lane] = exons[q.first_exon + lane]; S.marks[lane] = 0; }
+    __syncthreads();
+    // ---- step 1: check_for_not_source_sink_factorization (:2111-2125), check_exon_start_end (:1989-2019)
+    if (!refused) {
+      if (ne == 1 && (S.ex[0].EST_start < 0 || (uint32_t)S.ex[0].EST_start >= q.est_len)) cr.verdict = 1;
+      else {
+        bool bad = false;
+        if (lane < ne) {
+          const pgpu_factor f = S.ex[lane];
+          const int pe = lane ? S.ex[lane - 1].EST_end : -1, pg = lane ? S.ex[lane - 1].GEN_end : -1;
+          bad = f.EST_start > f.EST_end || f.GEN_start > f.GEN_end || f.EST_start < pe || f.GEN_start < pg;
+        }
+        if (__any(bad)) cr.verdict = 2;
+      }
+    }
+    // ---- step 2: handle_endpoints (:2127-2301): end 0 the head, end 1 the tail (of the list as the head left it)
+    for (uint32_t end = 0; end < 2 && !refused && cr.verdict == 0; ++end) {
+      const uint32_t at = end == 0 ? lo : hi - 1;
+      const pgpu_factor f = S.ex[at];
+      const uint32_t la = (uint32_t)(f.EST_end - f.EST_start + 1), lb = (uint32_t)(f.GEN_end - f.GEN_start + 1);
+      if (la > MAX_END || lb > MAX_END) { refused = true; break; }
+      DevJob job;
+      job.a = est + f.EST_start; job.b = T + f.GEN_start; job.la = la; job.lb = lb;
+      job.p0 = job.p1 = job.p2 = job.tail = 0;
+      job.ws_off = 0; job.str_off = ws_dirs; job.out_idx = 0; job.r_class = 1;
+      // The host sized the workspace for every alignment a query of this call can reach (the loop in the entry), so none
+      // of the three size tests below can fire today.  They keep a later slip in that sizing from writing out of bounds,
+      // and it does not pass for a refusal: the call then fails as a whole with PGPU_EDEVICE.
+      const bool band = la > 64u && (la > lb ? la - lb : lb - la) <= ALIGN_BAND_HALF;
+      if (rows_bytes(la, lb) > ws_rows || (la <= 64u && dirs_wave(lb) > ws_dirs) || (band && dirs_band(la) > ws_dirs)) {
+        if (lane == 0) atomicOr(undersized, 1u);
+        refused = true; break;
+      }
+      if (la <= 64u) {                                                      // lev_wave<ALIGN>
+        lev_wave_body<1, MODE_ALIGN>(job, res, w, lane);
+        own_stores_visible();
+        align_traceback_wave(job, res, w, w, lane, S.win, S.path);
+      } else {                                                              // align_band, settled inside the band or refused
+        if (!band) { refused = true; break; }
+        bool same = la == lb;
+        if (same) for (uint32_t k = lane; k < la; k += 64) same = same && job.a[k] == job.b[k];
+        if (__all(same)) {                                                  // identity alignment (compute-alignments.c:48-58)
+          if (lane == 0) { res->status = 0; res->v[0] = 0; res->v[1] = (int32_t)la; res->v[5] = 1; }
+          own_stores_visible();
+          align_traceback_wave(job, res, w, w, lane, S.win, S.path);        // its identity branch
+        } else {
+          uint32_t* const bdirs = reinterpret_cast<uint32_t*>(w);
+          const uint32_t score = align_band_sweep(job.a, la, job.b, lb, lane, bdirs);
+          if (score > ALIGN_BAND_K) { refused = true; break; }
+          if (lane == 0) { res->status = 0; res->v[0] = (int32_t)score; res->v[5] = 0; }
+          own_stores_visible();
+          align_band_traceback(job, res, bdirs, w, lane, S.win, S.path);
+        }
+      }
+      own_stores_visible();                                                 // the two rows and their length
+      const uint32_t dim = (uint32_t)__builtin_amdgcn_readfirstlane(res->v[1]);
+      uint8_t* const ea = w + (uint32_t)__builtin_amdgcn_readfirstlane((int)res->str[0]);
+      uint8_t* const ga = w + (uint32_t)__builtin_amdgcn_readfirstlane((int)res->str[1]);
+      __syncthreads();                                                      // the traceback is done with the window
+      if (end == 0) {
+        uint32_t matches = 0, cf = 0, ce = 0;
+        bool stop = false;
+        for (uint32_t base = 0; base < dim && !stop; base += 64) {
+          const uint32_t col = base + lane;
+          const uint32_t xe = col < dim ? ea[col] : 0u, xg = col < dim ? ga[col] : 0u;
+          const unsigned long long eq = __ballot(col < dim && xe == xg), eg = __ballot(xe == '-'), gg = __ballot(xg == '-');
+          head_walk_window(eq, eg, gg, dim - base < 64u ? dim - base : 64u, matches, cf, ce, stop);
+        }
+        if (stop) {
+          if (lane == 0) { S.ex[at].EST_start = f.EST_start + (int)(cf - matches); S.ex[at].GEN_start = f.GEN_start + (int)(ce - matches); }
+        } else {
+          if (lane == 0) S.marks[at] |= 1u;
+          ++lo;
+        }
+      } else {
+        int j = (int)dim - 1, cf = (int)la - 1, ce = (int)lb - 1;
+        uint32_t matches = 0;
+        bool stop = false, done = false;
+        while (!done) {
+          const uint32_t wb = j >= 63 ? (uint32_t)j - 63u : 0u;            // lane t holds column wb + t
+          const uint32_t col = wb + lane;
+          const uint32_t xe = col < dim ? ea[col] : 0u, xg = col < dim ? ga[col] : 0u;
+          const unsigned long long eq = __ballot(col < dim && xe == xg), eg = __ballot(xe == '-'), gg = __ballot(xg == '-');
+          done = tail_walk_window(eq, eg, gg, wb, j, matches, cf, ce, stop);
+        }
+        int est_cl = cf + (int)matches, gen_cl = ce + (int)matches;
+        MemRows rows{ea, ga};
+        close_tail_gaps(rows, dim, (uint32_t)(j + (int)matches + 1), est_cl, gen_cl);
+        if (gen_cl >= 0) {
+          if (lane == 0) { S.ex[at].EST_end = f.EST_start + est_cl; S.ex[at].GEN_end = f.GEN_start + gen_cl; }
+        } else {
+          if (lane == 0) S.marks[at] |= 1u;
+          --hi;
+        }
+      }
+      __syncthreads();                                                      // the exon as trimmed, for every lane
+      if (lo == hi) cr.verdict = 3;
+    }
+    // ---- step 3: clean_external_exons (:1706-1825)
+    for (uint32_t end = 0; end < 2 && !refused && cr.verdict == 0; ++end) {
+      const uint32_t at = end == 0 ? lo : hi - 1;
+      const pgpu_factor f = S.ex[at];
+      const int gl = f.GEN_end - f.GEN_start + 1, el = f.EST_end - f.EST_start + 1;
+      bool ok = gl >= 10;
+      if (ok && gl < 20) {
+        if (hi - lo < 2) ok = false;                                       // no neighbour to share an intron with
+        else if (end == 0) {
+          const int acc = S.ex[lo + 1].GEN_start;
+          ok = site(f.GEN_end + 1) == 'G' && (site(f.GEN_end + 2) == 'T' || site(f.GEN_end + 2) == 'C') &&
+               site(acc - 2) == 'A' && site(acc - 1) == 'G';
+        } else {
+          const int don = S.ex[hi - 2].GEN_end;
+          ok = site(f.GEN_start - 2) == 'A' && site(f.GEN_start - 1) == 'G' &&
+               site(don + 1) == 'G' && (site(don + 2) == 'T' || site(don + 2) == 'C');
+        }
+        // an edit distance > 0: the two pieces differ as byte strings
+        if (ok) {
+          bool differ = gl != el;
+          if (!differ && (int)lane < gl) differ = T[f.GEN_start + (int)lane] != est[f.EST_start + (int)lane];
+          ok = !__any(differ);
+        }
+      }
+      if (!ok) {
+        if (lane == 0) S.marks[at] |= 2u;
+        if (end == 0) ++lo; else --hi;
+        if (lo == hi) cr.verdict = 4;
+      }
+    }
+    __syncthreads();
+    // ---- step 4: clean_low_complexity_exons_2 (:1667-1704)
+    if (!refused && cr.verdict == 0) {
+      unsigned long long bad = 0ull;
+      for (uint32_t i = lo; i < hi; ++i) {
+        const pgpu_factor f = S.ex[i];
+        if (f.GEN_start > f.GEN_end) continue;
+        DevJob job;
+        job.a = T + f.GEN_start; job.la = (uint32_t)(f.GEN_end - f.GEN_start + 1);
+        job.b = est + f.EST_start; job.lb = f.EST_end >= f.EST_start ? (uint32_t)(f.EST_end - f.EST_start + 1) : 0u;
+        const unsigned long long thr = (unsigned long long)__double_as_longlong(q.complexity_threshold);
+        job.p0 = 0; job.p1 = (uint32_t)thr; job.p2 = (uint32_t)(thr >> 32); job.tail = 1;
+        job.ws_off = 0; job.str_off = 0; job.out_idx = 0; job.r_class = 1;
+        const uint32_t fl = (uint32_t)__builtin_amdgcn_readfirstlane((int)dust_flags_wave(job, lane));
+        if (fl) {
+          bad |= 1ull << i;
+          if (lane == 0) S.marks[i] |= (uint8_t)(fl << 2);
+        }
+      }
+      best_run(S.ex, bad, lo, hi);
+      if (lo == hi) cr.verdict = 5;
+    }
+    // ---- step 5: clean_noisy_exons (:1842-1898), only_internals = false
+    if (!refused && cr.verdict == 0) {
+      bool wide = false;
+      if (lane >= lo && lane < hi) {
+        const pgpu_factor f = S.ex[lane];
+        wide = f.GEN_start <= f.GEN_end && max_edit_for_exon((uint32_t)(f.GEN_end - f.GEN_start + 1)) > MAX_KBAND;
+      }
+      refused = __any(wide);
+    }
+    if (!refused && cr.verdict == 0) {
+      unsigned long long bad = 0ull;
+      for (uint32_t i = lo; i < hi; ++i) {
+        const pgpu_factor f = S.ex[i];
+        bool ok = false;
+        if (f.GEN_start <= f.GEN_end) {
+          DevJob job;
+          job.a = T + f.GEN_start; job.la = (uint32_t)(f.GEN_end - f.GEN_start + 1);
+          job.b = est + f.EST_start; job.lb = f.EST_end >= f.EST_start ? (uint32_t)(f.EST_end - f.EST_start + 1) : 0u;
+          job.p0 = max_edit_for_exon(job.la); job.p1 = job.p2 = job.tail = 0;
+          job.ws_off = 0; job.str_off = 0; job.out_idx = 0; job.r_class = 1;
+          lev_wave_body<1, MODE_KBAND>(job, res, w, lane);
+          own_stores_visible();
+          ok = __builtin_amdgcn_readfirstlane(res->v[0]) != 0;
+          own_stores_visible();                                            // read before the next exon's answer lands
+        }
+        if (!ok) {
+          bad |= 1ull << i;
+          if (lane == 0) S.marks[i] |= 16u;
+        }
+      }
+      best_run(S.ex, bad, lo, hi);
+      if (lo == hi) cr.verdict = 6;
+    }
+    // ---- step 6: check_est_coverage (:2303-2321)
+    if (!refused && cr.verdict == 0) {
+      const int cover = S.ex[hi - 1].EST_end - S.ex[lo].EST_start + 1;
+      if (!((double)cover / (double)q.est_len >= (double)0.35f)) cr.verdict = 7;
+    }
+    __syncthreads();                                                        // the marks
+    if (refused) { cr.status = PGPU_ERANGE; cr.verdict = 0; }
+    else {
+      if (cr.verdict == 0 || cr.verdict == 7) {
+        cr.first_kept = lo; cr.n_kept = hi - lo;
+        if (lane == 0) {
+          out_exons[q.first_exon + lo].EST_start = S.ex[lo].EST_start; out_exons[q.first_exon + lo].GEN_start = S.ex[lo].GEN_start;
+          out_exons[q.first_exon + hi - 1].EST_end = S.ex[hi - 1].EST_end; out_exons[q.first_exon + hi - 1].GEN_end = S.ex[hi - 1].GEN_end;
+        }
+      }
+      if (lane < ne) out_marks[q.first_exon + lane] = S.marks[lane];
+    }
+    if (lane == 0) out[c] = cr;
+  }
+}
+
+thread_local double t_clean_ms = 0.0;
+
+constexpr unsigned WAVES_PER_CU = 16;       // resident queries per compute unit the grid is sized for
+constexpr size_t WS_BUDGET = (size_t)256 << 20;      // bytes of per-wave workspace a call allocates at the most (see the grid)
+
+// what step 1 says of a query, on the host: the coordinate rules that follow hold for the queries that pass it
+bool passes_step1(const pgpu_factor* ex, uint32_t ne, uint32_t est_len) {
+  if (ne == 1 && (ex[0].EST_start < 0 || (uint32_t)ex[0].EST_start >= est_len)) return false;
+  int pe = -1, pg = -1;
+  for (uint32_t k = 0; k < ne; ++k) {
+    if (ex[k].EST_start > ex[k].EST_end || ex[k].GEN_start > ex[k].GEN_end || ex[k].EST_start < pe || ex[k].GEN_start < pg) return false;
+    pe = ex[k].EST_end; pg = ex[k].GEN_end;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" double pgpu_index_clean_chains_kernel_ms(void) { return t_clean_ms; }
+
+extern "C" int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                       const pgpu_factor* exons, size_t n_exons_total, const pgpu_clean_query* q, size_t n,
+                                       pgpu_factor* out_exons, uint8_t* out_marks, pgpu_clean_result* out) {
+  t_clean_ms = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
+  static_assert(sizeof(pgpu_clean_query) == 32 && sizeof(pgpu_clean_result) == 16 && sizeof(pgpu_factor) == 16, "ABI layout");
+  if (!ctx || !idx || (n && (!q || !out)) || (ests_len && !ests) || (n_exons_total && (!exons || !out_exons || !out_marks)))
+    return PGPU_EINVAL;
+  if (n > 0x7fffffffull || n_exons_total > 0x7fffffffull)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 queries or exons in one call");
+  const size_t glen = pgpu_index_length(idx);
+  // which exons a query has named already; calloc, for no exception may cross this boundary
+  struct Freed { uint8_t* p; ~Freed() { free(p); } } named_block{ (uint8_t*)calloc(n_exons_total ? n_exons_total : 1, 1) };
+  uint8_t* const named = named_block.p;
+  if (!named) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "no memory for the table of the exons the queries name");
+  // the workspace of one wave holds the longest end-exon alignment of the call (trimming only shortens an exon)
+  size_t ws_dirs = 256, ws_rows = 16;
+  for (size_t i = 0; i < n; ++i) {
+    const pgpu_clean_query& x = q[i];
+    bool ok = x.est_off <= ests_len && x.est_len <= ests_len - x.est_off && x.est_len != 0 && x.est_len <= 0x7fffffffu &&
+              x.reserved == 0 && x.n_exons != 0 && x.first_exon <= n_exons_total && x.n_exons <= n_exons_total - x.first_exon;
+    for (uint32_t k = 0; ok && k < x.n_exons; ++k) {
+      ok = !named[x.first_exon + k] && factor_ok(exons[x.first_exon + k], x.est_len, glen);
+      named[x.first_exon + k] = 1;
+    }
+    if (ok && passes_step1(exons + x.first_exon, x.n_exons, x.est_len)) {
+      const pgpu_factor& head = exons[x.first_exon];
+      const pgpu_factor& tail = exons[x.first_exon + x.n_exons - 1];
+      // the my_asserts of :2140-2141 and :2199-2200
+      ok = head.EST_start >= 0 && head.GEN_start >= 0 && (uint32_t)tail.EST_end < x.est_len && (size_t)tail.GEN_end < glen;
+      if (ok && x.n_exons <= PGPU_CLEAN_MAX_EXONS) {
+        for (const pgpu_factor* f : { &head, &tail }) {
+          const uint32_t la = (uint32_t)(f->EST_end - f->EST_start + 1), lb = (uint32_t)(f->GEN_end - f->GEN_start + 1);
+          if (la > PGPU_CLEAN_MAX_END_EXON || lb > PGPU_CLEAN_MAX_END_EXON) continue;      // refused on the device
+          const size_t d = la <= 64u ? dirs_wave(lb) : dirs_band(la);
+          if (d > ws_dirs) ws_dirs = d;
+          // (a single exon is aligned again as the head step trimmed it: to 64 EST bytes or fewer, lev_wave<ALIGN> takes it)
+          if (x.n_exons == 1 && la > 64u && dirs_wave(lb) > ws_dirs) ws_dirs = dirs_wave(lb);
+          if (rows_bytes(la, lb) > ws_rows) ws_rows = rows_bytes(la, lb);
+        }
+      }
+    }
+    if (!ok)
+      return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad clean query (a range past its buffer, an empty EST, reserved != 0, no exon, an exon two "
+                                             "queries share, a coordinate outside what it indexes, or an end exon that begins in "
+                                             "front of or ends behind its sequence)");
+  }
+  if (n == 0) {
+    if (n_exons_total) { memcpy(out_exons, exons, n_exons_total * sizeof(pgpu_factor)); memset(out_marks, 0, n_exons_total); }
+    return PGPU_OK;
+  }
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  QueryCall call(ctx, "clean chains");
+  const hipStream_t st = call.st;
+  int dev = 0, cus = 0;
+  TRY_HIP(hipGetDevice(&dev));
+  TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const size_t ws_wave = (ws_dirs + ws_rows + sizeof(DevResult) + 255) & ~(size_t)255;      // as clean_kernel lays it out
+  // the grid: 16 waves per compute unit, fewer where one long end exon has made the workspace of a wave large (266 KB for
+  // 4096 genomic bytes under lev_wave<ALIGN>): the workspaces together stay within WS_BUDGET, at one wave per compute
+  // unit at the least, so that one such query costs the batch some parallelism and not an allocation of a gigabyte
+  size_t waves = (size_t)cus * WAVES_PER_CU;
+  if (waves * ws_wave > WS_BUDGET) waves = WS_BUDGET / ws_wave > (size_t)cus ? WS_BUDGET / ws_wave : (size_t)cus;
+  if (waves > n) waves = n;
+  const size_t ex_bytes = n_exons_total * sizeof(pgpu_factor);
+  const size_t o_ex = up256(ests_len + 64), o_q = o_ex + up256(ex_bytes), o_oex = o_q + up256(n * sizeof(pgpu_clean_query)),
+               o_mk = o_oex + up256(ex_bytes), o_r = o_mk + up256(n_exons_total), o_flag = o_r + up256(n * sizeof(pgpu_clean_result)),
+               o_ws = o_flag + 256, total = o_ws + waves * ws_wave;
+  TRY_HIP(hipMalloc((void**)&call.d, total));
+  TRY_HIP(call.timing_events(1));
+  TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_ex, exons, ex_bytes, hipMemcpyHostToDevice, st));
+  TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof(pgpu_clean_query), hipMemcpyHostToDevice, st));
+  // exons no query names, and the exons of a query that is refused: the output starts as a copy of the input, marks as 0
+  TRY_HIP(hipMemcpyAsync(call.d + o_oex, call.d + o_ex, ex_bytes, hipMemcpyDeviceToDevice, st));
+  TRY_HIP(hipMemsetAsync(call.d + o_mk, 0, n_exons_total, st));
+  TRY_HIP(hipMemsetAsync(call.d + o_flag, 0, sizeof(uint32_t), st));
+  TRY_HIP(call.record(0));
+  hipLaunchKernelGGL(clean_kernel, dim3((unsigned)waves), dim3(64), 0, st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
+                     (const pgpu_factor*)(call.d + o_ex), (const pgpu_clean_query*)(call.d + o_q), (uint32_t)n, call.d + o_ws,
+                     ws_dirs, ws_rows, (pgpu_factor*)(call.d + o_oex), call.d + o_mk, (pgpu_clean_result*)(call.d + o_r),
+                     (uint32_t*)(call.d + o_flag));
+  TRY_HIP(call.record(1));
+  TRY_HIP(hipMemcpyAsync(out_exons, call.d + o_oex, ex_bytes, hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMemcpyAsync(out_marks, call.d + o_mk, n_exons_total, hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMemcpyAsync(out, call.d + o_r, n * sizeof(pgpu_clean_result), hipMemcpyDeviceToHost, st));
+  uint32_t undersized = 0;
+  TRY_HIP(hipMemcpyAsync(&undersized, call.d + o_flag, sizeof undersized, hipMemcpyDeviceToHost, st));
+  TRY_HIP(pgpu_ctx_wait(ctx));
+  TRY_HIP(hipGetLastError());
+  if (undersized)
+    return pgpu_ctx_fail(ctx, PGPU_EDEVICE, "clean chains: the workspace of a wave was sized too small for an end-exon alignment");
+  call.elapsed_ms(0, &t_clean_ms);
+  return PGPU_OK;
+}
