@@ -415,19 +415,22 @@ class Index:
     def refine_introns_kernel_ms(self):
         return self.ctx.L.pgpu_index_refine_introns_kernel_ms()
 
+    def _chained_raw(self, fn, query_struct, result_struct, result_dtype, ests, exons, queries, n):
+        """a chained entry (one query = one list of exons) as it is: (rc, out_exons, one byte per exon, results)"""
+        import numpy as np
+        out_exons = np.zeros(len(exons), dtype=np.dtype(FACTOR_DTYPE))
+        out_bytes = np.zeros(len(exons), dtype=np.uint8)
+        res = np.zeros(n, dtype=np.dtype(result_dtype))
+        rc = fn(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)), len(exons),
+                queries.ctypes.data_as(C.POINTER(query_struct)), n, out_exons.ctypes.data_as(C.POINTER(Factor)),
+                out_bytes.ctypes.data_as(C.POINTER(C.c_uint8)), res.ctypes.data_as(C.POINTER(result_struct)))
+        return rc, out_exons, out_bytes, res
+
     def refine_chains_raw(self, ests: bytes, exons, queries, n: int):
         """One pgpu_index_refine_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
         CHAIN_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of CHAIN_RESULT_DTYPE)."""
-        import numpy as np
-        out_exons = np.zeros(len(exons), dtype=np.dtype(FACTOR_DTYPE))
-        out_steps = np.zeros(len(exons), dtype=np.uint8)
-        res = np.zeros(n, dtype=np.dtype(CHAIN_RESULT_DTYPE))
-        rc = self.ctx.L.pgpu_index_refine_chains(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)),
-                                                 len(exons), queries.ctypes.data_as(C.POINTER(ChainQuery)), n,
-                                                 out_exons.ctypes.data_as(C.POINTER(Factor)),
-                                                 out_steps.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                 res.ctypes.data_as(C.POINTER(ChainResult)))
-        return rc, out_exons, out_steps, res
+        return self._chained_raw(self.ctx.L.pgpu_index_refine_chains, ChainQuery, ChainResult, CHAIN_RESULT_DTYPE,
+                                 ests, exons, queries, n)
 
     def refine_chains(self, ests: bytes, exons, queries):
         """The reference's refinement loop over every factorization `queries` names (windows, gap alignment and border
@@ -442,16 +445,8 @@ class Index:
     def clean_chains_raw(self, ests: bytes, exons, queries, n: int):
         """One pgpu_index_clean_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
         CLEAN_QUERY_DTYPE.  Returns (rc, out_exons, out_marks, results as a numpy array of CLEAN_RESULT_DTYPE)."""
-        import numpy as np
-        out_exons = np.zeros(len(exons), dtype=np.dtype(FACTOR_DTYPE))
-        out_marks = np.zeros(len(exons), dtype=np.uint8)
-        res = np.zeros(n, dtype=np.dtype(CLEAN_RESULT_DTYPE))
-        rc = self.ctx.L.pgpu_index_clean_chains(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)),
-                                                len(exons), queries.ctypes.data_as(C.POINTER(CleanQuery)), n,
-                                                out_exons.ctypes.data_as(C.POINTER(Factor)),
-                                                out_marks.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                res.ctypes.data_as(C.POINTER(CleanResult)))
-        return rc, out_exons, out_marks, res
+        return self._chained_raw(self.ctx.L.pgpu_index_clean_chains, CleanQuery, CleanResult, CLEAN_RESULT_DTYPE,
+                                 ests, exons, queries, n)
 
     def clean_chains(self, ests: bytes, exons, queries):
         """The reference's cleaning steps over every candidate factorization `queries` names (end-exon alignments and

@@ -160,8 +160,6 @@ void chain_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __re
 
 thread_local double t_chain_ms = 0.0;
 
-constexpr unsigned WAVES_PER_CU = 16;       // resident chains per compute unit the grid is sized for
-
 }  // namespace
 
 extern "C" double pgpu_index_refine_chains_kernel_ms(void) { return t_chain_ms; }
@@ -172,65 +170,35 @@ extern "C" int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, co
                                         pgpu_factor* out_exons, uint8_t* out_steps, pgpu_chain_result* out) {
   t_chain_ms = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
   static_assert(sizeof(pgpu_chain_query) == 40 && sizeof(pgpu_chain_result) == 16 && sizeof(pgpu_factor) == 16, "ABI layout");
-  if (!ctx || !idx || (n && (!q || !out)) || (ests_len && !ests) || (n_exons_total && (!exons || !out_exons || !out_steps)))
-    return PGPU_EINVAL;
-  if (n > 0x7fffffffull || n_exons_total > 0x7fffffffull)
-    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 chains or exons in one call");
+  NamedExons named;
+  const int begun = chained_begin(ctx, idx, ests, ests_len, exons, n_exons_total, q, n, out_exons, out_steps, out, "chains", named);
+  if (begun != CHAINED_GO) return begun;
   const size_t glen = pgpu_index_length(idx);
-  // which exons a chain has named already; calloc, for no exception may cross this boundary
-  struct Freed { uint8_t* p; ~Freed() { free(p); } } named_block{ (uint8_t*)calloc(n_exons_total ? n_exons_total : 1, 1) };
-  uint8_t* const named = named_block.p;
-  if (!named) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "no memory for the table of the exons the chains name");
-  for (size_t i = 0; i < n; ++i) {
-    const pgpu_chain_query& x = q[i];
-    bool ok = x.est_off <= ests_len && x.est_len <= ests_len - x.est_off && x.est_len <= 0x7fffffffu && x.reserved == 0 &&
-              x.n_exons != 0 && x.first_exon <= n_exons_total && x.n_exons <= n_exons_total - x.first_exon &&
-              suffpref_ok(x.suffpref_length_on_est, x.suffpref_length_for_intron, x.suffpref_length_on_gen);
-    for (uint32_t k = 0; ok && k < x.n_exons; ++k) {
-      const pgpu_factor& f = exons[x.first_exon + k];
-      ok = !named[x.first_exon + k] && factor_ok(f, x.est_len, glen);
-      named[x.first_exon + k] = 1;
-      if (ok && k + 1 < x.n_exons) {                       // the my_asserts of :52-53, on fields no earlier step writes
-        const pgpu_factor& g = exons[x.first_exon + k + 1];
-        ok = f.EST_end < g.EST_start && f.GEN_end < g.GEN_start;
-      }
-    }
-    if (!ok)
-      return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad chain query (a range past its buffer, reserved != 0, no exon, an exon two chains "
-                                             "share, a donor that is not in front of its acceptor, or a coordinate outside what it "
-                                             "indexes)");
-  }
-  if (n == 0) {
-    if (n_exons_total) { memcpy(out_exons, exons, n_exons_total * sizeof(pgpu_factor)); memset(out_steps, 0, n_exons_total); }
-    return PGPU_OK;
-  }
+  // a chain's own rules: the suffpref lengths, and the my_asserts of :52-53, on fields no earlier step writes
+  const auto own = [](const pgpu_chain_query& x, const pgpu_factor* ex) {
+    bool ok = suffpref_ok(x.suffpref_length_on_est, x.suffpref_length_for_intron, x.suffpref_length_on_gen);
+    for (uint32_t k = 0; ok && k + 1 < x.n_exons; ++k) ok = ex[k].EST_end < ex[k + 1].EST_start && ex[k].GEN_end < ex[k + 1].GEN_start;
+    return ok;
+  };
+  if (!chained_queries_ok(q, n, ests_len, exons, n_exons_total, glen, named.p, own))
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad chain query (a range past its buffer, reserved != 0, no exon, an exon two chains "
+                                           "share, a donor that is not in front of its acceptor, or a coordinate outside what it "
+                                           "indexes)");
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   QueryCall call(ctx, "refine chains");
-  const hipStream_t st = call.st;
-  int dev = 0, cus = 0;
-  TRY_HIP(hipGetDevice(&dev));
-  TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const size_t waves = n < (size_t)cus * WAVES_PER_CU ? n : (size_t)cus * WAVES_PER_CU;
-  const size_t ex_bytes = n_exons_total * sizeof(pgpu_factor);
-  const size_t o_ex = up256(ests_len + 64), o_q = o_ex + up256(ex_bytes), o_oex = o_q + up256(n * sizeof(pgpu_chain_query)),
-               o_st = o_oex + up256(ex_bytes), o_r = o_st + up256(n_exons_total), o_ws = o_r + up256(n * sizeof(pgpu_chain_result)),
-               total = o_ws + waves * WS_WAVE;
-  TRY_HIP(hipMalloc((void**)&call.d, total));
+  size_t waves = 0, cus = 0;
+  TRY_HIP(chained_waves(n, waves, cus));
+  const ChainedLayout L = chained_layout(ests_len, n_exons_total, n, sizeof *q, sizeof *out, 0, waves * WS_WAVE);
+  TRY_HIP(hipMalloc((void**)&call.d, L.total));
   TRY_HIP(call.timing_events(1));
-  if (ests_len) TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(call.d + o_ex, exons, ex_bytes, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof(pgpu_chain_query), hipMemcpyHostToDevice, st));
-  // exons no query names: the output starts as a copy of the input, and their steps as 0
-  TRY_HIP(hipMemcpyAsync(call.d + o_oex, call.d + o_ex, ex_bytes, hipMemcpyDeviceToDevice, st));
-  TRY_HIP(hipMemsetAsync(call.d + o_st, 0, n_exons_total, st));
+  TRY_HIP(chained_upload(call, L, ests, exons, q));
   TRY_HIP(call.record(0));
-  hipLaunchKernelGGL(chain_kernel, dim3((unsigned)waves), dim3(64), 0, st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
-                     (const pgpu_factor*)(call.d + o_ex), (const pgpu_chain_query*)(call.d + o_q), (uint32_t)n, call.d + o_ws,
-                     (pgpu_factor*)(call.d + o_oex), call.d + o_st, (pgpu_chain_result*)(call.d + o_r));
+  hipLaunchKernelGGL(chain_kernel, dim3((unsigned)waves), dim3(64), 0, call.st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
+                     (const pgpu_factor*)(call.d + L.exons), (const pgpu_chain_query*)(call.d + L.queries), (uint32_t)n,
+                     call.d + L.ws, (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes,
+                     (pgpu_chain_result*)(call.d + L.results));
   TRY_HIP(call.record(1));
-  TRY_HIP(hipMemcpyAsync(out_exons, call.d + o_oex, ex_bytes, hipMemcpyDeviceToHost, st));
-  TRY_HIP(hipMemcpyAsync(out_steps, call.d + o_st, n_exons_total, hipMemcpyDeviceToHost, st));
-  TRY_HIP(hipMemcpyAsync(out, call.d + o_r, n * sizeof(pgpu_chain_result), hipMemcpyDeviceToHost, st));
+  TRY_HIP(chained_download(call, L, out_exons, out_steps, out));
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
   call.elapsed_ms(0, &t_chain_ms);

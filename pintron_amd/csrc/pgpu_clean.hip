@@ -303,7 +303,6 @@ void clean_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __re
 
 thread_local double t_clean_ms = 0.0;
 
-constexpr unsigned WAVES_PER_CU = 16;       // resident queries per compute unit the grid is sized for
 constexpr size_t WS_BUDGET = (size_t)256 << 20;      // bytes of per-wave workspace a call allocates at the most (see the grid)
 
 // what step 1 says of a query, on the host: the coordinate rules that follow hold for the queries that pass it
@@ -326,88 +325,63 @@ extern "C" int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, con
                                        pgpu_factor* out_exons, uint8_t* out_marks, pgpu_clean_result* out) {
   t_clean_ms = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
   static_assert(sizeof(pgpu_clean_query) == 32 && sizeof(pgpu_clean_result) == 16 && sizeof(pgpu_factor) == 16, "ABI layout");
-  if (!ctx || !idx || (n && (!q || !out)) || (ests_len && !ests) || (n_exons_total && (!exons || !out_exons || !out_marks)))
-    return PGPU_EINVAL;
-  if (n > 0x7fffffffull || n_exons_total > 0x7fffffffull)
-    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 queries or exons in one call");
+  NamedExons named;
+  const int begun = chained_begin(ctx, idx, ests, ests_len, exons, n_exons_total, q, n, out_exons, out_marks, out, "queries", named);
+  if (begun != CHAINED_GO) return begun;
   const size_t glen = pgpu_index_length(idx);
-  // which exons a query has named already; calloc, for no exception may cross this boundary
-  struct Freed { uint8_t* p; ~Freed() { free(p); } } named_block{ (uint8_t*)calloc(n_exons_total ? n_exons_total : 1, 1) };
-  uint8_t* const named = named_block.p;
-  if (!named) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "no memory for the table of the exons the queries name");
   // the workspace of one wave holds the longest end-exon alignment of the call (trimming only shortens an exon)
   size_t ws_dirs = 256, ws_rows = 16;
-  for (size_t i = 0; i < n; ++i) {
-    const pgpu_clean_query& x = q[i];
-    bool ok = x.est_off <= ests_len && x.est_len <= ests_len - x.est_off && x.est_len != 0 && x.est_len <= 0x7fffffffu &&
-              x.reserved == 0 && x.n_exons != 0 && x.first_exon <= n_exons_total && x.n_exons <= n_exons_total - x.first_exon;
-    for (uint32_t k = 0; ok && k < x.n_exons; ++k) {
-      ok = !named[x.first_exon + k] && factor_ok(exons[x.first_exon + k], x.est_len, glen);
-      named[x.first_exon + k] = 1;
+  // a clean query's own rules: an EST of at least one byte, and for what passes step 1 the my_asserts of :2140-2141 and
+  // :2199-2200 on its end exons -- which, in the same pass, size the workspace
+  const auto own = [&](const pgpu_clean_query& x, const pgpu_factor* ex) {
+    if (x.est_len == 0) return false;
+    if (!passes_step1(ex, x.n_exons, x.est_len)) return true;
+    const pgpu_factor& head = ex[0];
+    const pgpu_factor& tail = ex[x.n_exons - 1];
+    if (head.EST_start < 0 || head.GEN_start < 0 || (uint32_t)tail.EST_end >= x.est_len || (size_t)tail.GEN_end >= glen) return false;
+    if (x.n_exons > PGPU_CLEAN_MAX_EXONS) return true;                                    // refused on the device
+    for (const pgpu_factor* f : { &head, &tail }) {
+      const uint32_t la = (uint32_t)(f->EST_end - f->EST_start + 1), lb = (uint32_t)(f->GEN_end - f->GEN_start + 1);
+      if (la > PGPU_CLEAN_MAX_END_EXON || lb > PGPU_CLEAN_MAX_END_EXON) continue;      // refused on the device
+      const size_t d = la <= 64u ? dirs_wave(lb) : dirs_band(la);
+      if (d > ws_dirs) ws_dirs = d;
+      // (a single exon is aligned again as the head step trimmed it: to 64 EST bytes or fewer, lev_wave<ALIGN> takes it)
+      if (x.n_exons == 1 && la > 64u && dirs_wave(lb) > ws_dirs) ws_dirs = dirs_wave(lb);
+      if (rows_bytes(la, lb) > ws_rows) ws_rows = rows_bytes(la, lb);
     }
-    if (ok && passes_step1(exons + x.first_exon, x.n_exons, x.est_len)) {
-      const pgpu_factor& head = exons[x.first_exon];
-      const pgpu_factor& tail = exons[x.first_exon + x.n_exons - 1];
-      // the my_asserts of :2140-2141 and :2199-2200
-      ok = head.EST_start >= 0 && head.GEN_start >= 0 && (uint32_t)tail.EST_end < x.est_len && (size_t)tail.GEN_end < glen;
-      if (ok && x.n_exons <= PGPU_CLEAN_MAX_EXONS) {
-        for (const pgpu_factor* f : { &head, &tail }) {
-          const uint32_t la = (uint32_t)(f->EST_end - f->EST_start + 1), lb = (uint32_t)(f->GEN_end - f->GEN_start + 1);
-          if (la > PGPU_CLEAN_MAX_END_EXON || lb > PGPU_CLEAN_MAX_END_EXON) continue;      // refused on the device
-          const size_t d = la <= 64u ? dirs_wave(lb) : dirs_band(la);
-          if (d > ws_dirs) ws_dirs = d;
-          // (a single exon is aligned again as the head step trimmed it: to 64 EST bytes or fewer, lev_wave<ALIGN> takes it)
-          if (x.n_exons == 1 && la > 64u && dirs_wave(lb) > ws_dirs) ws_dirs = dirs_wave(lb);
-          if (rows_bytes(la, lb) > ws_rows) ws_rows = rows_bytes(la, lb);
-        }
-      }
-    }
-    if (!ok)
-      return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad clean query (a range past its buffer, an empty EST, reserved != 0, no exon, an exon two "
-                                             "queries share, a coordinate outside what it indexes, or an end exon that begins in "
-                                             "front of or ends behind its sequence)");
-  }
-  if (n == 0) {
-    if (n_exons_total) { memcpy(out_exons, exons, n_exons_total * sizeof(pgpu_factor)); memset(out_marks, 0, n_exons_total); }
-    return PGPU_OK;
-  }
+    return true;
+  };
+  if (!chained_queries_ok(q, n, ests_len, exons, n_exons_total, glen, named.p, own))
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad clean query (a range past its buffer, an empty EST, reserved != 0, no exon, an exon two "
+                                           "queries share, a coordinate outside what it indexes, or an end exon that begins in "
+                                           "front of or ends behind its sequence)");
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   QueryCall call(ctx, "clean chains");
-  const hipStream_t st = call.st;
-  int dev = 0, cus = 0;
-  TRY_HIP(hipGetDevice(&dev));
-  TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   const size_t ws_wave = (ws_dirs + ws_rows + sizeof(DevResult) + 255) & ~(size_t)255;      // as clean_kernel lays it out
   // the grid: 16 waves per compute unit, fewer where one long end exon has made the workspace of a wave large (266 KB for
   // 4096 genomic bytes under lev_wave<ALIGN>): the workspaces together stay within WS_BUDGET, at one wave per compute
   // unit at the least, so that one such query costs the batch some parallelism and not an allocation of a gigabyte
-  size_t waves = (size_t)cus * WAVES_PER_CU;
-  if (waves * ws_wave > WS_BUDGET) waves = WS_BUDGET / ws_wave > (size_t)cus ? WS_BUDGET / ws_wave : (size_t)cus;
-  if (waves > n) waves = n;
-  const size_t ex_bytes = n_exons_total * sizeof(pgpu_factor);
-  const size_t o_ex = up256(ests_len + 64), o_q = o_ex + up256(ex_bytes), o_oex = o_q + up256(n * sizeof(pgpu_clean_query)),
-               o_mk = o_oex + up256(ex_bytes), o_r = o_mk + up256(n_exons_total), o_flag = o_r + up256(n * sizeof(pgpu_clean_result)),
-               o_ws = o_flag + 256, total = o_ws + waves * ws_wave;
-  TRY_HIP(hipMalloc((void**)&call.d, total));
+  size_t waves = 0, cus = 0;
+  TRY_HIP(chained_waves(n, waves, cus));
+  if (waves * ws_wave > WS_BUDGET) {
+    const size_t fit = WS_BUDGET / ws_wave > cus ? WS_BUDGET / ws_wave : cus;
+    if (waves > fit) waves = fit;
+  }
+  const ChainedLayout L = chained_layout(ests_len, n_exons_total, n, sizeof *q, sizeof *out, 256, waves * ws_wave);
+  TRY_HIP(hipMalloc((void**)&call.d, L.total));
+  uint32_t* const d_undersized = (uint32_t*)(call.d + L.extra);      // the flag of a workspace sized too small, in the extra slot
   TRY_HIP(call.timing_events(1));
-  TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(call.d + o_ex, exons, ex_bytes, hipMemcpyHostToDevice, st));
-  TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof(pgpu_clean_query), hipMemcpyHostToDevice, st));
-  // exons no query names, and the exons of a query that is refused: the output starts as a copy of the input, marks as 0
-  TRY_HIP(hipMemcpyAsync(call.d + o_oex, call.d + o_ex, ex_bytes, hipMemcpyDeviceToDevice, st));
-  TRY_HIP(hipMemsetAsync(call.d + o_mk, 0, n_exons_total, st));
-  TRY_HIP(hipMemsetAsync(call.d + o_flag, 0, sizeof(uint32_t), st));
+  TRY_HIP(chained_upload(call, L, ests, exons, q));
+  TRY_HIP(hipMemsetAsync(d_undersized, 0, sizeof(uint32_t), call.st));
   TRY_HIP(call.record(0));
-  hipLaunchKernelGGL(clean_kernel, dim3((unsigned)waves), dim3(64), 0, st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
-                     (const pgpu_factor*)(call.d + o_ex), (const pgpu_clean_query*)(call.d + o_q), (uint32_t)n, call.d + o_ws,
-                     ws_dirs, ws_rows, (pgpu_factor*)(call.d + o_oex), call.d + o_mk, (pgpu_clean_result*)(call.d + o_r),
-                     (uint32_t*)(call.d + o_flag));
+  hipLaunchKernelGGL(clean_kernel, dim3((unsigned)waves), dim3(64), 0, call.st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
+                     (const pgpu_factor*)(call.d + L.exons), (const pgpu_clean_query*)(call.d + L.queries), (uint32_t)n,
+                     call.d + L.ws, ws_dirs, ws_rows, (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes,
+                     (pgpu_clean_result*)(call.d + L.results), d_undersized);
   TRY_HIP(call.record(1));
-  TRY_HIP(hipMemcpyAsync(out_exons, call.d + o_oex, ex_bytes, hipMemcpyDeviceToHost, st));
-  TRY_HIP(hipMemcpyAsync(out_marks, call.d + o_mk, n_exons_total, hipMemcpyDeviceToHost, st));
-  TRY_HIP(hipMemcpyAsync(out, call.d + o_r, n * sizeof(pgpu_clean_result), hipMemcpyDeviceToHost, st));
+  TRY_HIP(chained_download(call, L, out_exons, out_marks, out));
   uint32_t undersized = 0;
-  TRY_HIP(hipMemcpyAsync(&undersized, call.d + o_flag, sizeof undersized, hipMemcpyDeviceToHost, st));
+  TRY_HIP(hipMemcpyAsync(&undersized, d_undersized, sizeof undersized, hipMemcpyDeviceToHost, call.st));
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
   if (undersized)

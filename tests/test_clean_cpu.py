@@ -7,10 +7,11 @@ import re
 
 import numpy as np
 
+import binding_lib as BL
 import clean_lib as CL
 import refine_lib as RL
 
-HEADER = os.path.join(RL.ROOT, "include", "pintron_gpu.h")
+HEADER = BL.HEADER
 
 
 def test_restatement_equals_the_fixture_on_every_case():
@@ -105,21 +106,6 @@ def test_caps_and_einval_rules_of_the_restatement():
     assert not CL.einval(len(est), len(gen), e2, [_query(est, ex)])
 
 
-def _header_struct(name):
-    text = open(HEADER).read()
-    m = re.search(r"typedef struct \{((?:(?!typedef).)*?)\}\s*" + name + r";\s*/\*\s*(\d+) bytes", text, re.S)
-    assert m, name
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        ctype, names = decl.split(None, 1)
-        fields += [(n.strip(), ctype) for n in names.split(",")]
-    return fields, int(m.group(2))
-
-
 def test_binding_matches_the_header():
     from pintron_amd import capi
     assert "pgpu_index_clean_chains" in capi.EXPORTS and "pgpu_index_clean_chains_kernel_ms" in capi.EXPORTS
@@ -131,16 +117,7 @@ def test_binding_matches_the_header():
     assert int(re.search(r"#define PGPU_CLEAN_MAX_END_EXON\s+(\d+)", text).group(1)) == capi.CLEAN_MAX_END_EXON == CL.MAX_END_EXON == 4096
     band = open(os.path.join(RL.ROOT, "pintron_amd", "csrc", "pgpu_internal.h")).read()
     assert int(re.search(r"constexpr uint32_t ALIGN_BAND_HALF = (\d+)u;", band).group(1)) == CL.BAND_HALF == CL.MAX_KBAND
-    size_of = {"uint64_t": 8, "uint32_t": 4, "int32_t": 4, "double": 8}
     for cname, struct, dtype in (("pgpu_clean_query", capi.CleanQuery, capi.CLEAN_QUERY_DTYPE),
                                  ("pgpu_clean_result", capi.CleanResult, capi.CLEAN_RESULT_DTYPE)):
-        fields, size = _header_struct(cname)
-        assert [f for f, _ in fields] == [f for f, _ in struct._fields_] == [f for f, _ in dtype], cname
-        off = 0
-        dt = np.dtype(dtype)
-        for f, ctype in fields:                          # no padding anywhere: every field follows the one before
-            assert getattr(struct, f).offset == off == dt.fields[f][1], (cname, f)
-            assert getattr(struct, f).size == size_of[ctype] == dt.fields[f][0].itemsize, (cname, f)
-            off += size_of[ctype]
-        assert off == size == C.sizeof(struct) == dt.itemsize, cname
+        BL.assert_layout(cname, struct, dtype)
     assert np.dtype(capi.FACTOR_DTYPE).itemsize == C.sizeof(capi.Factor) == 16

@@ -3,14 +3,15 @@
 the millisecond slot is set with timing on and 0.0 without it, with the same answers; a call refused with PGPU_EINVAL
 resets the slot and leaves its message; the context answers the same afterwards; an empty call is PGPU_OK with the slot
 at 0.  For pgpu_index_find also the PGPU_ENOSPC round and a second context on the same index.  The answers are held
-against the CPU restatements (bytes.find, tests/small_exon_lib.py, tests/refine_lib.py, tests/chain_lib.py), never
-against the library alone; the messages are the literal texts of the source."""
+against the CPU restatements (bytes.find, tests/small_exon_lib.py, tests/refine_lib.py, tests/chain_lib.py,
+tests/clean_lib.py), never against the library alone; the messages are the literal texts of the source."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import chain_lib as CL
+import clean_lib as KL
 import refine_lib as RL
 import small_exon_lib as SL
 
@@ -23,6 +24,8 @@ MESSAGES = {
                       "the acceptor, or a coordinate outside what it indexes)",
     "refine_chains": "bad chain query (a range past its buffer, reserved != 0, no exon, an exon two chains share, a donor that "
                      "is not in front of its acceptor, or a coordinate outside what it indexes)",
+    "clean_chains": "bad clean query (a range past its buffer, an empty EST, reserved != 0, no exon, an exon two queries share, a "
+                    "coordinate outside what it indexes, or an end exon that begins in front of or ends behind its sequence)",
 }
 
 
@@ -168,12 +171,39 @@ def world(O):
     e.cq = cq
     e.ms = lambda: (idx.refine_chains_kernel_ms(),)
 
+    # clean_chains: the chain's two exons twice, under the complexity thresholds 20.0 and 0.32.  (The restatement takes
+    # them past step 1 and within every cap: both queries end at the coverage check, with different marks on the way.)
+    kbatch = [(est, exons, 20.0), (est, exons, 0.32)]
+    kests, kexons, kq = KL.batch_arrays(kbatch)
+    want_k = [KL.clean(x, gen, ex, thr) for x, ex, thr in kbatch]
+    assert all(w[0] == KL.OK and w[1] not in (1, 2) for w in want_k) and want_k[0][5] != want_k[1][5]
+    kbad = kq.copy()
+    kbad["reserved"][1] = 1
+
+    def cleaned(q, n, marks_fill=0):
+        """as capi's clean_chains_raw, with out_marks filled beforehand"""
+        oe, om = np.zeros_like(kexons), np.full(len(kexons), marks_fill, dtype=np.uint8)
+        res = np.zeros(n, dtype=np.dtype(capi.CLEAN_RESULT_DTYPE))
+        rc = ctx.L.pgpu_index_clean_chains(ctx.h, idx.h, kests, len(kests), kexons.ctypes.data_as(C.POINTER(capi.Factor)), len(kexons),
+                                           q.ctypes.data_as(C.POINTER(capi.CleanQuery)), n, oe.ctypes.data_as(C.POINTER(capi.Factor)),
+                                           om.ctypes.data_as(C.POINTER(C.c_uint8)), res.ctypes.data_as(C.POINTER(capi.CleanResult)))
+        return rc, oe.tobytes() + om.tobytes() + res.tobytes()
+    e = entries["clean_chains"] = Entry()
+    e.good = lambda: cleaned(kq, len(kq))
+    e.want = b"".join(a.tobytes() for a in KL.expect_arrays(kexons, want_k))
+    e.bad = lambda: cleaned(kbad, len(kbad))[0]
+    e.empty = lambda: cleaned(kq, 0)[0]
+    e.empty_answer = kexons.tobytes() + bytes(len(kexons))          # n == 0: the exons copied, the marks zeroed
+    e.cleaned = cleaned
+    e.kq = kq
+    e.ms = lambda: (idx.clean_chains_kernel_ms(),)
+
     yield capi, ctx, idx, gen, entries
     idx.close()
     ctx.close()
 
 
-@pytest.mark.parametrize("name", ["find", "small_exons", "refine_introns", "refine_chains"])
+@pytest.mark.parametrize("name", ["find", "small_exons", "refine_introns", "refine_chains", "clean_chains"])
 def test_the_contract_of_a_timed_entry(world, name):
     capi, ctx, idx, gen, entries = world
     e = entries[name]
@@ -201,6 +231,13 @@ def test_an_empty_chain_call_copies_the_exons(world):
     capi, ctx, idx, gen, entries = world
     e = entries["refine_chains"]
     rc, answer = e.chains(e.cq, 0)
+    assert rc == capi.PGPU_OK and answer == e.empty_answer
+
+
+def test_an_empty_clean_call_copies_the_exons_and_zeroes_the_marks(world):
+    capi, ctx, idx, gen, entries = world
+    e = entries["clean_chains"]
+    rc, answer = e.cleaned(e.kq, 0, marks_fill=0xA5)
     assert rc == capi.PGPU_OK and answer == e.empty_answer
 
 

@@ -1,5 +1,6 @@
 """CPU: the parts of pintron_amd/csrc/pgpu_query_call.h that make no HIP call (the rounding of the device offsets, the
-return code of a HIP error, the range checks of the refine and chain queries), in a stand-alone program
+return code of a HIP error, the range checks of the refine and chain queries, the validator and the device layout the two
+chained entries share), in a stand-alone program
 (tests/hostcheck/query_call_check.cpp) built by the host compiler with AddressSanitizer and UBSan and run directly."""
 import os
 import subprocess
