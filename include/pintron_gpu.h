@@ -375,6 +375,65 @@ int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* es
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_clean_chains_kernel_ms(void);
 
+/* check_gap_errors of a factorization, chained: FILTER 4 of get_EST_factorizations (src/est-factorizations.c:416-433, the
+ * routine at :1462-1545), the step between the cleaning steps above and the refinement loop of pgpu_index_refine_chains --
+ * for every unaligned EST gap between two exons a border refinement (refine_borders, src/refine.c:85-192) against the
+ * intron, the four exon ends that face the gap moved, the distances summed against the threshold of :1465, and the exons
+ * whose genomic gap is at most 3 merged.  One query = one factorization; the call is synchronous and batched like
+ * pgpu_index_clean_chains, and its exon arrays have the same shape.  FILTER 1 and FILTER 3 compare candidates with each
+ * other and stay with the caller, as add_if_not_exists does. */
+#define PGPU_GAPS_MAX_EXONS    64   /* exons of one factorization; beyond: PGPU_ERANGE for that query            */
+#define PGPU_GAPS_MAX_EST_GAP  64   /* bytes of one EST gap (the BORDERS pattern: one row per lane); beyond: same */
+#define PGPU_GAPS_MAX_ERRORS   20   /* threshold_ed of :1465 */
+typedef struct {
+  uint64_t est_off; uint32_t est_len;   /* EST_seq = ests + est_off, est_len bytes, 1 .. 2^31 - 1 */
+  uint32_t first_exon, n_exons;         /* the factorization = exons[first_exon .. first_exon + n_exons) */
+  uint32_t reserved;                    /* 0 */
+} pgpu_gaps_query;                      /* 24 bytes: 0, 8, 12, 16, 20; no padding */
+typedef struct {
+  int32_t  status;       /* PGPU_OK or PGPU_ERANGE */
+  uint32_t verdict;      /* 0 kept; 1 dropped: the distances of its gaps sum to more than 20 (:1517) */
+  uint32_t total_edit;   /* tot_out_edit_distance */
+  uint32_t n_kept;       /* exons left after the merging loop (verdict 0); 0 otherwise */
+} pgpu_gaps_result;      /* 16 bytes */
+
+/*  - The border loop (:1475-1514), for each adjacent pair (d, a) in order: gapP = a.EST_start - d.EST_end - 1 and
+ *    gapT = a.GEN_start - d.GEN_end - 1, both taken from the input -- a gap writes only the four ends that face it, so the
+ *    strings of every gap are the input's.  When gapP > 0: general_refine_borders(p, gapP, 0, gapP, t, gapT, max_errs =
+ *    gapP) with p = the EST gap and t = the whole genomic gap, read from the resident sequence, with `tail = 0`: the
+ *    reference works on NUL-terminated copies (real_substring, :1489-1490), so getBursetFrequency_adaptor sees a terminator
+ *    behind t, not the acceptor exon.  The result is PGPU_DP_BORDERS's, bit for bit: plain byte equality with N no
+ *    wildcard, t_win = min(2 gapP, gapT), the first cut with the smallest total, ties broken by a strictly larger Burset
+ *    frequency.  Then, as :1502-1506: d.EST_end += off_p; a.EST_start = d.EST_end + 1; d.GEN_end += off_t1;
+ *    a.GEN_start -= gapT - off_t2.
+ *  - refine_borders cannot refuse here: its total is at most len_p (every row minimum is at most the row's first column)
+ *    and max_errs = len_p, so the `ok == false` branch of :1508 is dead.
+ *  - The verdict: a total above PGPU_GAPS_MAX_ERRORS is verdict 1 (:1517).
+ *  - The merging loop (:1522-1542), on verdict 0, with a running donor: an exon whose GEN_start - donor.GEN_end - 1 <= 3
+ *    (negative included) gives its EST_end and GEN_end to the donor and is removed; any other exon becomes the donor.
+ *  - out_exons (n_exons_total entries) and out_steps (n_exons_total bytes) are parallel to exons: same indices; exons no
+ *    query names are copied, with step 0.  out_steps[i] for the exon at place i >= 1 of a query: bits 0-6 are 0 when the EST
+ *    gap in front of it was empty, else 1 + that gap's edit distance (1 .. 65); bit 7: the exon was merged into the one
+ *    before it.  A merged exon's out_exons entry holds the exon as the border loop left it, the donor's entry holds the
+ *    merged ends.  On verdict 1 out_exons is what the border loop left, and no bit 7 is set.
+ *  - Caps refuse only the query that meets them: its result is PGPU_ERANGE with verdict, total_edit and n_kept 0, its exons
+ *    are copied unchanged and their steps are 0.  More than PGPU_GAPS_MAX_EXONS exons; an EST gap longer than
+ *    PGPU_GAPS_MAX_EST_GAP.  The genomic gap has no cap of its own: only its first and last t_win <= 128 bytes are read.
+ *  - PGPU_EINVAL for the whole call: a null pointer (no message); n_exons == 0; first_exon + n_exons > n_exons_total or
+ *    est_off + est_len > ests_len; est_len == 0 or > 2^31 - 1; reserved != 0; two queries share an exon; a factor coordinate
+ *    outside what pgpu_index_refine_introns accepts; for some adjacent pair exon[i].EST_end >= exon[i + 1].EST_start or
+ *    exon[i].GEN_end >= exon[i + 1].GEN_start; for some adjacent pair gapP > gapT (the FATAL of :1485, where the reference
+ *    ends the program).  All of these are properties of the input and are checked up front; with them both pieces of
+ *    every gap lie inside their strings.  A 0 byte inside the EST is a letter like any other.
+ *  - n == 0 is PGPU_OK (out_exons = exons, out_steps = 0); n_exons == 1 is verdict 0, n_kept 1.  idx may be built or
+ *    loaded. */
+int pgpu_index_gap_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                          const pgpu_factor* exons, size_t n_exons_total, const pgpu_gaps_query* q, size_t n,
+                          pgpu_factor* out_exons, uint8_t* out_steps, pgpu_gaps_result* out);
+/* HIP-event time of the kernel of the calling thread's last pgpu_index_gap_chains on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_gap_chains_kernel_ms(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */

@@ -93,6 +93,15 @@ class CleanResult(C.Structure):    # pgpu_clean_result
     _fields_ = [("status", C.c_int32), ("verdict", C.c_uint32), ("first_kept", C.c_uint32), ("n_kept", C.c_uint32)]
 
 
+class GapsQuery(C.Structure):      # pgpu_gaps_query
+    _fields_ = [("est_off", C.c_uint64), ("est_len", C.c_uint32), ("first_exon", C.c_uint32), ("n_exons", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class GapsResult(C.Structure):     # pgpu_gaps_result
+    _fields_ = [("status", C.c_int32), ("verdict", C.c_uint32), ("total_edit", C.c_uint32), ("n_kept", C.c_uint32)]
+
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -113,6 +122,9 @@ CLEAN_MAX_EXONS, CLEAN_MAX_END_EXON = 64, 4096
 CLEAN_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u4"), ("reserved", "<u4"),
                      ("complexity_threshold", "<f8")]
 CLEAN_RESULT_DTYPE = [("status", "<i4"), ("verdict", "<u4"), ("first_kept", "<u4"), ("n_kept", "<u4")]
+GAPS_MAX_EXONS, GAPS_MAX_EST_GAP, GAPS_MAX_ERRORS = 64, 64, 20
+GAPS_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u4"), ("reserved", "<u4")]
+GAPS_RESULT_DTYPE = [("status", "<i4"), ("verdict", "<u4"), ("total_edit", "<u4"), ("n_kept", "<u4")]
 
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
@@ -125,6 +137,7 @@ assert C.sizeof(Intron) == 8 and C.sizeof(SexonQuery) == 40 and C.sizeof(SexonRe
 assert C.sizeof(Factor) == 16 and C.sizeof(RefineQuery) == 96 and C.sizeof(RefineResult) == 48
 assert C.sizeof(ChainQuery) == 40 and C.sizeof(ChainResult) == 16
 assert C.sizeof(CleanQuery) == 32 and C.sizeof(CleanResult) == 16
+assert C.sizeof(GapsQuery) == 24 and C.sizeof(GapsResult) == 16
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -135,6 +148,7 @@ EXPORTS = [
     "pgpu_index_refine_introns", "pgpu_index_refine_introns_kernel_ms",
     "pgpu_index_refine_chains", "pgpu_index_refine_chains_kernel_ms",
     "pgpu_index_clean_chains", "pgpu_index_clean_chains_kernel_ms",
+    "pgpu_index_gap_chains", "pgpu_index_gap_chains_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -203,6 +217,10 @@ def lib():
                                               C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(CleanResult)]
         L.pgpu_index_clean_chains_kernel_ms.argtypes = []
         L.pgpu_index_clean_chains_kernel_ms.restype = C.c_double
+        L.pgpu_index_gap_chains.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(GapsQuery), sz,
+                                            C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(GapsResult)]
+        L.pgpu_index_gap_chains_kernel_ms.argtypes = []
+        L.pgpu_index_gap_chains_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -458,6 +476,23 @@ class Index:
 
     def clean_chains_kernel_ms(self):
         return self.ctx.L.pgpu_index_clean_chains_kernel_ms()
+
+    def gap_chains_raw(self, ests: bytes, exons, queries, n: int):
+        """One pgpu_index_gap_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+        GAPS_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of GAPS_RESULT_DTYPE)."""
+        return self._chained_raw(self.ctx.L.pgpu_index_gap_chains, GapsQuery, GapsResult, GAPS_RESULT_DTYPE,
+                                 ests, exons, queries, n)
+
+    def gap_chains(self, ests: bytes, exons, queries):
+        """The reference's check_gap_errors over every factorization `queries` names (a border refinement per unaligned
+        EST gap, the four ends moved, the distances summed, close exons merged, chained on the device): (out_exons,
+        out_steps, results) as numpy arrays."""
+        rc, out_exons, out_steps, res = self.gap_chains_raw(ests, exons, queries, len(queries))
+        self.ctx.check(rc)
+        return out_exons, out_steps, res
+
+    def gap_chains_kernel_ms(self):
+        return self.ctx.L.pgpu_index_gap_chains_kernel_ms()
 
     def close(self):
         if self.h:

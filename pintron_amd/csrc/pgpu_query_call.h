@@ -1,8 +1,9 @@
-// The host side of a query on the resident index, once: what the six entries pgpu_index_find, pgpu_index_classify,
-// pgpu_index_small_exons, pgpu_index_refine_introns, pgpu_index_refine_chains and pgpu_index_clean_chains share around
-// their kernels.  An entry validates, lays out its device block, copies in, launches, copies out and waits, as
-// straight-line code; the QueryCall on its stack owns what has to be given back whichever way the entry returns.  The two
-// chained entries (one query = one list of exons, chained on the device) share more: the chained path at the end.
+// The host side of a query on the resident index, once: what the seven entries pgpu_index_find, pgpu_index_classify,
+// pgpu_index_small_exons, pgpu_index_refine_introns, pgpu_index_refine_chains, pgpu_index_clean_chains and
+// pgpu_index_gap_chains share around their kernels.  An entry validates, lays out its device block, copies in, launches,
+// copies out and waits, as straight-line code; the QueryCall on its stack owns what has to be given back whichever way the
+// entry returns.  The three chained entries (one query = one list of exons, chained on the device) share more: the chained
+// path at the end.
 //
 // The contract of every entry (tests/test_gpu_query_calls.py): a refused call and an empty one leave the entry's
 // millisecond slot at 0; with pgpu_set_timing off the slot stays 0 and the answers are the same; a call that fails in
@@ -86,10 +87,11 @@ struct QueryCall {
     if (e_ != hipSuccess) return call.fail(e_);         \
   } while (0)
 
-// ---- The chained path: pgpu_index_refine_chains and pgpu_index_clean_chains.  Both query structs begin with est_off,
-// est_len, first_exon, n_exons and reserved; both calls answer with out_exons and one byte per exon, parallel to `exons`
-// (an exon no query names: a copy and byte 0; an empty call: that for every exon, without a device call), and with one
-// result per query.  An entry keeps what the other does differently: its own rules, its workspace and its kernel.
+// ---- The chained path: pgpu_index_refine_chains, pgpu_index_clean_chains and pgpu_index_gap_chains.  Their query structs
+// begin with est_off, est_len, first_exon, n_exons and reserved; the calls answer with out_exons and one byte per exon,
+// parallel to `exons` (an exon no query names: a copy and byte 0; an empty call: that for every exon, without a device
+// call), and with one result per query.  An entry keeps what the others do differently: its own rules, its workspace and
+// its kernel.
 
 // which exons a query has named already; calloc, for no exception may cross the C boundary
 struct NamedExons { uint8_t* p = nullptr; ~NamedExons() { free(p); } };

@@ -258,8 +258,8 @@ __device__ __forceinline__ int acgt_code(uint32_t c) {
   }
 }
 
-// getBursetFrequency_adaptor (src/refine-intron.c:362-374): only the BORDERS mode of lev_wave_body asks it, and the unit
-// that instantiates that mode (pgpu_dp_kernels.hip) defines it, with its table
+// getBursetFrequency_adaptor (src/refine-intron.c:362-374): only the BORDERS mode of lev_wave_body asks it, and a unit
+// that instantiates that mode (pgpu_dp_kernels.hip, pgpu_gaps.hip) includes pgpu_burset.h, which defines it with its table
 __device__ int burset_adaptor(const uint8_t* t, uint32_t avail, uint32_t cut1, uint32_t cut2);
 
 // ---------------------------------------------------------------------------------------------
