@@ -173,28 +173,9 @@ __device__ __forceinline__ void lev_sweep_coop(const Operand rows, const uint32_
             DirPack<R> dp;
             if constexpr (DIRS) dp.clear();
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-              const uint32_t left = cur[r];
-              bool match = rc[r] == ch;
-              if constexpr (WILD) match = match || ch_n || is_n(rc[r]);
-              uint32_t v = diag + (match ? 0u : 1u);
-              if constexpr (DIRS) {
-                // ComputeAlignMatrix tie-break: diagonal, then up (dir 1), then left (dir 2), strict >
-                uint32_t d = 0;
-                if (v > up + 1) { v = up + 1; d = 1; }
-                if (v > left + 1) { v = left + 1; d = 2; }
-                dp.set(r, d);
-              } else {
-                v = min(v, min(up + 1, left + 1));
-              }
-              if constexpr (ROWMIN) {
-                if (minv[r] > v) { minv[r] = v; minpos[r] = j; }
-              }
-              if constexpr (AFFIX) best.template consider<ASMALL>(rc[r] == ch, v, row0 + r + 1, j);
-              diag = left;
-              cur[r] = v;
-              up = v;
-            }
+            for (int r = 0; r < R; ++r)
+              lev_cell<R, WILD, DIRS, ROWMIN, AFFIX, false, ASMALL>(r, rc[r], ch, ch_n, diag, up, cur[r], minv[r], minpos[r], best, dp,
+                                                                    row0 + r + 1, j, 0u);
             diag_in = in_val;
             out = up | (ch << 24);
             if constexpr (DIRS) dp.store(dir_ws + ((size_t)s * (64u * COOP_W) + gl) * (R <= 4 ? 1u : R / 4));
@@ -212,51 +193,27 @@ __device__ __forceinline__ void lev_sweep_coop(const Operand rows, const uint32_
 // waves 0-3 and the reversed-string sweep on waves 4-7 of one 512-thread workgroup.
 template <int R>
 __device__ __forceinline__ void borders_coop_body(const DevJob& job, DevResult* res) {
-  extern __shared__ uint32_t lds[];      // hand-off [2][COOP_W-1][2][64], then pre, pre_pos, suf, suf_pos
+  extern __shared__ uint32_t lds[];      // hand-off [2][COOP_W-1][2][64], then the row minima (BordersMins)
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // scalar: branches on it are uniform
   const uint32_t sweep = wave / COOP_W, w = wave % COOP_W;
   const uint32_t len_p = job.la, len_t = job.lb, max_errs = job.p2;
   const uint32_t t_win = min(len_p + max_errs, len_t);
   uint32_t* hand = lds + sweep * ((COOP_W - 1) * 128);
-  uint32_t* pre = lds + 2 * (COOP_W - 1) * 128; uint32_t* pre_pos = pre + (len_p + 1);
-  uint32_t* suf = pre_pos + (len_p + 1); uint32_t* suf_pos = suf + (len_p + 1);
+  const BordersMins mins{lds + 2 * (COOP_W - 1) * 128, len_p};
   uint32_t cur[R], minv[R], minpos[R];
   AffixBest best = AFFIX_NONE;
   const Operand rows{job.a, len_p, sweep == 1}, cols{job.b, len_t, sweep == 1};
   lev_sweep_coop<R, true, false>(rows, len_p, cols, t_win, w, lane, hand, cur, minv, minpos, best);
-  uint32_t* mv = sweep ? suf : pre; uint32_t* mp = sweep ? suf_pos : pre_pos;
+  uint32_t* mv = sweep ? mins.suf : mins.pre; uint32_t* mp = sweep ? mins.suf_pos : mins.pre_pos;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const uint32_t i = (w * 64u + lane) * R + r + 1;
     if (i <= len_p) { mv[i] = minv[r]; mp[i] = minpos[r]; }
   }
-  if (threadIdx.x == 0) { pre[0] = 0; pre_pos[0] = 0; suf[0] = 0; suf_pos[0] = 0; }
+  if (threadIdx.x == 0) { mins.pre[0] = 0; mins.pre_pos[0] = 0; mins.suf[0] = 0; mins.suf_pos[0] = 0; }
   __syncthreads();
-  if (wave != 0) return;
-  // cut scan of src/refine.c:161-178: the first i in [lo, hi] with the smallest total, ties by the
-  // larger Burset frequency; 64 lanes scan i = lo + lane, lo + lane + 64, ... and then agree
-  const uint32_t avail = len_t + min(job.tail, 2u);
-  const uint32_t lo = job.p0, hi = job.p1 > job.p0 ? job.p1 : job.p0;   // i = lo is always a candidate
-  uint32_t bi = 0xFFFFFFFFu, bc = 0xFFFFFFFFu; int bf = -1;
-  for (uint32_t i = lo + lane; i <= hi; i += 64) {
-    const int freq = burset_adaptor(job.b, avail, pre_pos[i], len_t - suf_pos[len_p - i]);
-    const uint32_t c = pre[i] + suf[len_p - i];
-    if (bc > c || (bc == c && freq > bf)) { bc = c; bf = freq; bi = i; }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const uint32_t oc = __shfl_xor(bc, off), oi = __shfl_xor(bi, off);
-    const int of = __shfl_xor(bf, off);
-    if (oc < bc || (oc == bc && (of > bf || (of == bf && oi < bi)))) { bc = oc; bf = of; bi = oi; }
-  }
-  if (lane == 0) {
-    const uint32_t off_t1 = pre_pos[bi], off_t2 = suf_pos[len_p - bi];
-    res->status = 0;
-    res->v[0] = bc <= max_errs ? 1 : 0;
-    res->v[1] = (int32_t)bi; res->v[2] = (int32_t)off_t1;
-    res->v[3] = (int32_t)(len_t - off_t2); res->v[4] = (int32_t)bc;
-  }
+  if (wave == 0) borders_cut_scan(job, res, lane, mins.pre, mins.pre_pos, mins.suf, mins.suf_pos);
 }
 
 // every row class above 64 rows in one launch (one job per workgroup; see lev_any_kernel)
@@ -1027,10 +984,10 @@ void borders_slow_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* 
   const uint32_t len_p = job.la, len_t = job.lb, max_errs = job.p2;
   const uint32_t t_win = min(len_p + max_errs, len_t);
   uint32_t* diag = (uint32_t*)(ws + job.ws_off);
-  uint32_t* mins = diag + (size_t)3 * (len_p + 1);
+  const BordersMins mins{diag + (size_t)3 * (len_p + 1), len_p};
   for (int sweep = 0; sweep < 2; ++sweep) {
-    uint32_t* mv = mins + (size_t)(2 * sweep) * (len_p + 1);
-    uint32_t* mp = mv + (len_p + 1);
+    uint32_t* mv = sweep ? mins.suf : mins.pre;
+    uint32_t* mp = sweep ? mins.suf_pos : mins.pre_pos;
     const Operand rows{job.a, len_p, sweep == 1}, cols{job.b, len_t, sweep == 1};
     for (uint32_t i = threadIdx.x; i <= len_p; i += SLOW_BLOCK) { mv[i] = i; mp[i] = 0; }     // column 0: M[i][0] = i
     __syncthreads();
@@ -1054,7 +1011,8 @@ void borders_slow_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* 
     }
   }
   if (threadIdx.x != 0) return;
-  const uint32_t *pre = mins, *pre_pos = mins + (len_p + 1), *suf = mins + (size_t)2 * (len_p + 1), *suf_pos = mins + (size_t)3 * (len_p + 1);
+  // the scan of src/refine.c:161-178 as the reference writes it, by thread 0
+  const uint32_t *pre = mins.pre, *pre_pos = mins.pre_pos, *suf = mins.suf, *suf_pos = mins.suf_pos;
   const uint32_t avail = len_t + min(job.tail, 2u);
   const uint32_t lo = job.p0, hi = job.p1 > job.p0 ? job.p1 : job.p0;
   uint32_t bi = lo, bc = pre[lo] + suf[len_p - lo];
@@ -1064,10 +1022,7 @@ void borders_slow_kernel(const DevJob* __restrict__ jobs, int njobs, DevResult* 
     const uint32_t c = pre[i] + suf[len_p - i];
     if (bc > c || (bc == c && freq > bf)) { bc = c; bf = freq; bi = i; }
   }
-  res->status = 0;
-  res->v[0] = bc <= max_errs ? 1 : 0;
-  res->v[1] = (int32_t)bi; res->v[2] = (int32_t)pre_pos[bi];
-  res->v[3] = (int32_t)(len_t - suf_pos[len_p - bi]); res->v[4] = (int32_t)bc;
+  borders_write_result(job, res, pre_pos, suf_pos, bi, bc);
 }
 
 }  // namespace

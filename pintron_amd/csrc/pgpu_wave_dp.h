@@ -6,6 +6,8 @@
 // the K-band on the lanes), the alignment's traceback, the banded alignment with its traceback, and the trimming walks of
 // handle_endpoints.  pgpu_dp_kernels.hip runs them as the jobs of a plan, pgpu_clean.hip as the steps of a candidate's
 // cleaning chain.
+// Once, here: lev_cell, the recurrence of lev_sweep_strip and lev_sweep_coop (lev_sweep keeps its own copy: see lev_cell);
+// borders_cut_scan for the wave and cooperative forms of BORDERS, BordersMins and borders_write_result for all three.
 #pragma once
 
 #include "pgpu_internal.h"
@@ -262,6 +264,53 @@ __device__ __forceinline__ int acgt_code(uint32_t c) {
 // that instantiates that mode (pgpu_dp_kernels.hip, pgpu_gaps.hip) includes pgpu_burset.h, which defines it with its table
 __device__ int burset_adaptor(const uint8_t* t, uint32_t avail, uint32_t cut1, uint32_t cut2);
 
+// general_refine_borders (src/refine.c:105-192), what its wave, cooperative and slow forms share.  The row minima of the
+// prefix sweep and of the reversed-string sweep with the columns where they were first reached, [pre | pre_pos | suf |
+// suf_pos], each len_p + 1 words (row 0 included), carved out of one base pointer: BordersMins mins{base, len_p}.  An
+// aggregate, and helpers that take the pointers by value, on purpose: a constructor, or a helper that takes the struct or
+// a lane's minv[] / minpos[] by reference, changes the code the compiler makes for the sweeps beside it.
+struct BordersMins {
+  uint32_t* pre; uint32_t len_p;
+  uint32_t* pre_pos = pre + (len_p + 1);
+  uint32_t* suf = pre_pos + (len_p + 1);
+  uint32_t* suf_pos = suf + (len_p + 1);
+};
+
+// the answer for the cut at pattern position bi with bc errors in all (one thread writes it)
+__device__ __forceinline__ void borders_write_result(const DevJob& job, DevResult* res, const uint32_t* pre_pos,
+                                                     const uint32_t* suf_pos, const uint32_t bi, const uint32_t bc) {
+  const uint32_t len_p = job.la, len_t = job.lb, max_errs = job.p2;
+  const uint32_t off_t1 = pre_pos[bi], off_t2 = suf_pos[len_p - bi];
+  res->status = 0;
+  res->v[0] = bc <= max_errs ? 1 : 0;
+  res->v[1] = (int32_t)bi; res->v[2] = (int32_t)off_t1;
+  res->v[3] = (int32_t)(len_t - off_t2); res->v[4] = (int32_t)bc;
+}
+
+// cut scan of src/refine.c:161-178 by one wave: the first i in [lo, hi] with the smallest total, ties by the
+// larger Burset frequency.  The lanes take i = lo + lane, lo + lane + 64, ... (each reads its four
+// genomic characters at once instead of lane 0 walking <= len_p+1 dependent loads) and then agree.
+__device__ __forceinline__ void borders_cut_scan(const DevJob& job, DevResult* res, const uint32_t lane,
+                                                 const uint32_t* pre, const uint32_t* pre_pos,
+                                                 const uint32_t* suf, const uint32_t* suf_pos) {
+  const uint32_t len_p = job.la, len_t = job.lb;
+  const uint32_t avail = len_t + min(job.tail, 2u);
+  const uint32_t lo = job.p0, hi = job.p1 > job.p0 ? job.p1 : job.p0;   // i = lo is always a candidate
+  uint32_t bi = 0xFFFFFFFFu, bc = 0xFFFFFFFFu; int bf = -1;
+  for (uint32_t i = lo + lane; i <= hi; i += 64) {
+    const int freq = burset_adaptor(job.b, avail, pre_pos[i], len_t - suf_pos[len_p - i]);
+    const uint32_t c = pre[i] + suf[len_p - i];
+    if (bc > c || (bc == c && freq > bf)) { bc = c; bf = freq; bi = i; }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const uint32_t oc = __shfl_xor(bc, off), oi = __shfl_xor(bi, off);
+    const int of = __shfl_xor(bf, off);
+    if (oc < bc || (oc == bc && (of > bf || (of == bf && oi < bi)))) { bc = oc; bf = of; bi = oi; }
+  }
+  if (lane == 0) borders_write_result(job, res, pre_pos, suf_pos, bi, bc);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Levenshtein family
 // ---------------------------------------------------------------------------------------------
@@ -339,8 +388,40 @@ struct AffixBest {          // running best cut of find_longest_affix; s == 0: n
 };
 constexpr AffixBest AFFIX_NONE{1u, 0u, 0ull};
 
-// One column sweep.  On return cur[r] = M[row(l,r)][nc].
 constexpr uint32_t BAND_INF = 0x3FFFFFu;   // "outside the band"; stays below the 24-bit value field
+
+// The recurrence, once for lev_sweep_strip and lev_sweep_coop (pgpu_dp_kernels.hip): cell (row, j), the r-th of its lane.
+// In: diag = M[row-1][j-1], up = M[row-1][j], cur = M[row][j-1], rcr / ch = the row's and the column's character.  Out:
+// cur = up = M[row][j] and diag = M[row][j-1], i.e. what the lane's next row takes; with DIRS the cell's direction in dp,
+// with ROWMIN the row's first minimum, with AFFIX the running best cut.  lev_sweep keeps the same lines written out: with
+// any helper there, per column or per cell, dp_batch_kernel or lev_any_kernel<ED> fails what DESIGN.md section 8 holds them to.
+template <int R, bool WILD, bool DIRS, bool ROWMIN, bool AFFIX, bool BAND, bool ASMALL>
+__device__ __forceinline__ void lev_cell(const int r, const uint32_t rcr, const uint32_t ch, const bool ch_n, uint32_t& diag,
+                                         uint32_t& up, uint32_t& cur, uint32_t& minv, uint32_t& minpos, AffixBest& best, DirPack<R>& dp,
+                                         const uint32_t row, const uint32_t j, const uint32_t band_k) {
+  const uint32_t left = cur;
+  bool match = rcr == ch;
+  if constexpr (WILD) match = match || ch_n || is_n(rcr);
+  uint32_t v = diag + (match ? 0u : 1u);
+  if constexpr (DIRS) {
+    // ComputeAlignMatrix tie-break: diagonal, then up (dir 1), then left (dir 2), strict >
+    uint32_t d = 0;
+    if (v > up + 1) { v = up + 1; d = 1; }
+    if (v > left + 1) { v = left + 1; d = 2; }
+    dp.set(r, d);
+  } else {
+    v = min(v, min(up + 1, left + 1));
+  }
+  if constexpr (BAND) {
+    // K_band_edit_distance keeps cells with |column - row| <= k only; neighbours outside
+    // the band do not take part in the minimum (src/compute-alignments.c:375-443)
+    v = (j + band_k >= row && row + band_k >= j) ? min(v, BAND_INF) : BAND_INF;
+  }
+  if constexpr (ROWMIN) { if (minv > v) { minv = v; minpos = j; } }   // strict: first arg-min
+  // cut_weight = 2*v/(e+g) <= 0.17  <=>  200*v <= 17*(e+g)   (exact)
+  if constexpr (AFFIX) best.template consider<ASMALL>(rcr == ch, v, row, j);
+  diag = left; cur = v; up = v;
+}
 
 // Rows beyond 64*R are processed in horizontal STRIPS of 64*R rows by the same wave: the strip's
 // last row is written, per column, to a boundary array in the job's workspace (`bottom`) and is
@@ -405,37 +486,9 @@ __device__ __forceinline__ void lev_sweep_strip(const Operand rows, const uint32
       DirPack<R> dp;
       if constexpr (DIRS) dp.clear();
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const uint32_t left = cur[r];
-        bool match = rc[r] == ch;
-        if constexpr (WILD) match = match || ch_n || is_n(rc[r]);
-        uint32_t v = diag + (match ? 0u : 1u);
-        if constexpr (DIRS) {
-          // ComputeAlignMatrix tie-break: diagonal, then up (dir 1), then left (dir 2), strict >
-          uint32_t d = 0;
-          if (v > up + 1) { v = up + 1; d = 1; }
-          if (v > left + 1) { v = left + 1; d = 2; }
-          dp.set(r, d);
-        } else {
-          v = min(v, min(up + 1, left + 1));
-        }
-        if constexpr (BAND) {
-          // K_band_edit_distance keeps cells with |column - row| <= k only; neighbours outside
-          // the band do not take part in the minimum (src/compute-alignments.c:375-443)
-          const uint32_t row = row_base + row0 + r + 1;
-          v = (j + band_k >= row && row + band_k >= j) ? min(v, BAND_INF) : BAND_INF;
-        }
-        if constexpr (ROWMIN) {
-          if (minv[r] > v) { minv[r] = v; minpos[r] = j; }   // strict: first arg-min
-        }
-        if constexpr (AFFIX) {
-          // cut_weight = 2*v/(e+g) <= 0.17  <=>  200*v <= 17*(e+g)   (exact)
-          best.template consider<ASMALL>(rc[r] == ch, v, row_base + row0 + r + 1, j);
-        }
-        diag = left;
-        cur[r] = v;
-        up = v;
-      }
+      for (int r = 0; r < R; ++r)
+        lev_cell<R, WILD, DIRS, ROWMIN, AFFIX, BAND, ASMALL>(r, rc[r], ch, ch_n, diag, up, cur[r], minv[r], minpos[r], best, dp,
+                                                             row_base + row0 + r + 1, j, band_k);
       diag_in = in_val;
       out = up | (ch << 24);
       if constexpr (DIRS) dp.store(dir_ws + ((size_t)s * 64 + lane) * EB);
@@ -732,19 +785,16 @@ __device__ __forceinline__ void lev_wave_body(const DevJob& job, DevResult* res,
     store_row_value<R>(cur, lane, n, &res->v[0]);
     if (lane == 0) { res->status = 0; res->v[5] = 0; }
   } else if constexpr (MODE == MODE_BORDERS) {
-    // pre[], pre_pos[], suf[], suf_pos[], each len_p+1: the wave's own LDS region (several jobs per workgroup)
-    uint32_t* lds = wave_lds;
     const uint32_t len_p = job.la, len_t = job.lb, max_errs = job.p2;
     const uint32_t t_win = min(len_p + max_errs, len_t);
-    uint32_t* pre = lds; uint32_t* pre_pos = pre + (len_p + 1);
-    uint32_t* suf = pre_pos + (len_p + 1); uint32_t* suf_pos = suf + (len_p + 1);
+    const BordersMins mins{wave_lds, len_p};       // the wave's own LDS region (several jobs per workgroup)
     {
       const Operand rows{job.a, len_p, false}, cols{job.b, len_t, false};
       lev_sweep<R, false, false, true, false>(rows, len_p, cols, t_win, lane, cur, minv, minpos, best, nullptr);
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const uint32_t i = lane * R + r + 1;
-        if (i <= len_p) { pre[i] = minv[r]; pre_pos[i] = minpos[r]; }
+        if (i <= len_p) { mins.pre[i] = minv[r]; mins.pre_pos[i] = minpos[r]; }
       }
     }
     {
@@ -753,41 +803,16 @@ __device__ __forceinline__ void lev_wave_body(const DevJob& job, DevResult* res,
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const uint32_t i = lane * R + r + 1;
-        if (i <= len_p) { suf[i] = minv[r]; suf_pos[i] = minpos[r]; }
+        if (i <= len_p) { mins.suf[i] = minv[r]; mins.suf_pos[i] = minpos[r]; }
       }
     }
-    if (lane == 0) { pre[0] = 0; pre_pos[0] = 0; suf[0] = 0; suf_pos[0] = 0; }
+    if (lane == 0) { mins.pre[0] = 0; mins.pre_pos[0] = 0; mins.suf[0] = 0; mins.suf_pos[0] = 0; }
     // one wave produced the four arrays and one wave reads them: a wave-level hand-over (a workgroup
     // barrier would couple this wave to the unrelated jobs of its neighbours)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // cut scan of src/refine.c:161-178: the first i in [lo, hi] with the smallest total, ties by the
-    // larger Burset frequency.  The lanes take i = lo + lane, lo + lane + 64, ... (each reads its four
-    // genomic characters at once instead of lane 0 walking <= len_p+1 dependent loads) and then agree.
-    {
-      const uint32_t avail = len_t + min(job.tail, 2u);
-      const uint32_t lo = job.p0, hi = job.p1 > job.p0 ? job.p1 : job.p0;   // i = lo is always a candidate
-      uint32_t bi = 0xFFFFFFFFu, bc = 0xFFFFFFFFu; int bf = -1;
-      for (uint32_t i = lo + lane; i <= hi; i += 64) {
-        const int freq = burset_adaptor(job.b, avail, pre_pos[i], len_t - suf_pos[len_p - i]);
-        const uint32_t c = pre[i] + suf[len_p - i];
-        if (bc > c || (bc == c && freq > bf)) { bc = c; bf = freq; bi = i; }
-      }
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t oc = __shfl_xor(bc, off), oi = __shfl_xor(bi, off);
-        const int of = __shfl_xor(bf, off);
-        if (oc < bc || (oc == bc && (of > bf || (of == bf && oi < bi)))) { bc = oc; bf = of; bi = oi; }
-      }
-      if (lane == 0) {
-        const uint32_t off_t1 = pre_pos[bi], off_t2 = suf_pos[len_p - bi];
-        res->status = 0;
-        res->v[0] = bc <= max_errs ? 1 : 0;
-        res->v[1] = (int32_t)bi; res->v[2] = (int32_t)off_t1;
-        res->v[3] = (int32_t)(len_t - off_t2); res->v[4] = (int32_t)bc;
-      }
-    }
+    borders_cut_scan(job, res, lane, mins.pre, mins.pre_pos, mins.suf, mins.suf_pos);
   } else if constexpr (MODE == MODE_KBAND) {
     // K_band_edit_distance (src/compute-alignments.c:319-453): early exits in the reference's
     // order, then the banded DP (or the full matrix when 2k+1 >= n, :370-373).  rows = shorter.
