@@ -524,6 +524,95 @@ int pgpu_pairing_plan_fetch_meg(pgpu_ctx* ctx, pgpu_pairing_plan* plan, void* ou
 /* HIP-event time of the MEG kernels of the last run_meg (build + scan + emit) */
 double pgpu_pairing_plan_meg_ms(const pgpu_pairing_plan* plan);
 
+/* ------------------------------------------------------------------------------------------ */
+/* candidates -- the factorization of a MEG that is one path, from its record: what            */
+/* get_EST_factorizations does between the graph and the cleaning steps of                      */
+/* pgpu_index_clean_chains when get_subtree_embeddings (src/est-factorizations.c:597-762) has   */
+/* one embedding per vertex: update_embedding (:765-917, the Burset cut scan included) folded   */
+/* over the path from the sink backwards, then get_factorizations_from_embeddings               */
+/* (:1292-1356).  One record = one candidate at most; its exons have the shape the chained      */
+/* entries above take (run -> run_meg -> run_candidates -> clean -> gaps -> refine).            */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint32_t min_factor_len;     /* config->min_factor_len as the MEG was built with; 1 .. 2^24 */
+  int32_t  min_intron_length;  /* config->min_intron_length; only compared: any value         */
+} pgpu_cand_params;          /* 8 bytes */
+
+#define PGPU_CAND_NONE     0u   /* the record is flagged (PGPU_MEG_UNAVAILABLE or PGPU_MEG_TOO_COMPLEX): no graph to walk,
+                                   or the caller retries with longer factors */
+#define PGPU_CAND_NOT_PATH 1u   /* the graph is not one path: the caller enumerates (get_subtree_embeddings) */
+#define PGPU_CAND_REFUSED  2u   /* one path, and update_embedding returned NULL for some vertex: no candidate at all */
+#define PGPU_CAND_ONE      3u   /* one path, one embedding, one candidate */
+typedef struct {
+  uint32_t kind;               /* PGPU_CAND_* */
+  uint32_t work;               /* the units the enumeration counts (:626-629, :706-711): n_vertices, plus one per
+                                  update_embedding that returned an embedding, up to the refusal when there is one;
+                                  0 for NONE and NOT_PATH.  Comparing it with a budget stays with the caller */
+  uint32_t first_exon;         /* the candidate = exons[first_exon .. first_exon + n_exons); ONE only */
+  uint16_t n_exons;            /* >= 1 for ONE, else 0 */
+  uint16_t n_pairs;            /* pairings of the embedding; ONE only */
+} pgpu_cand_result;          /* 16 bytes */
+
+/*  - The path test: 2 <= n_vertices <= 64; vertex 0 is the source (p == INT32_MIN); from it the only out-edge is
+ *    followed until a vertex without one; no vertex is met twice and none on the way has an out-degree other than 1;
+ *    every vertex was visited and the last one is the sink (p == INT32_MAX - 200).  Anything else is NOT_PATH.
+ *  - The fold, from the sink backwards, with `head` the first pairing of the embedding so far, `node` the vertex in
+ *    front of it, L = min_factor_len and all of it in the reference's int arithmetic (:765-917):
+ *      head is the sink: a node with p < 0 (the source) refuses, any other node becomes the embedding;
+ *      node is the source: the embedding is copied;
+ *      small_delta = head.p + head.l - node.p, big_delta = head.t + head.l - node.t; refused unless both >= 2L,
+ *      small_delta - (node.l + head.l) <= 2L and small_delta - big_delta <= 2L;
+ *      when both deltas are >= node.l + head.l the two keep their lengths; otherwise the overlap is split:
+ *      ref_delta = min(small_delta, big_delta), node gets ref_delta / 2 and head the rest, clamped first on node.l,
+ *      else on head.l, and head begins that much in front of its old end on both strings;
+ *      gap_on_p / gap_on_t = head's start - node's start - node's length - 1 on either string, intron_len = gap_on_t -
+ *      max(gap_on_p, 0), intron_on_t = intron_len >= 0 && (min_intron_length == 0 || intron_len >= min_intron_length);
+ *      when small_delta < node.l + head.l and intron_on_t, the cut scan: for cut in [max(node.p + L, head.p),
+ *      min(head.p + head.l - L, node.p + node.l)] ascending, f = getBursetFrequency_adaptor(sequence,
+ *      cut - node.p + node.t, cut - head.p + head.t), kept when f >= the best so far (which starts at -1): the LAST of
+ *      equal cuts wins, and an empty range leaves best_cut = 0 and the arithmetic goes on with it; head then begins at
+ *      the cut and node ends in front of it;
+ *      refused unless gap_on_t <= 2L || intron_on_t (gap_on_t as it was BEFORE the cut scan).
+ *    The adaptor reads the resident sequence as a C string: a byte at or behind its end is the terminator, i.e.
+ *    frequency 0; cut2 < 2 gives 0; the lookup is case-insensitive, anything but ACGT gives 0.
+ *  - The exons (:1292-1356), over the embedding front to back: a pairing x opens an exon when x.t - GEN_end of the
+ *    exon before - 1 > 2L, otherwise it moves that exon's EST_end and GEN_end to its own end.  The embedding is never
+ *    stored: a step of the fold fixes the length of the node it adds and the start of the head it trims, nothing older
+ *    changes again, so the exons are produced back to front.
+ *  - exons of a call are compact, in record order; NONE, NOT_PATH and REFUSED records have none. */
+
+/* Plan form: the candidates of the records pgpu_pairing_plan_run_meg left in HBM; nothing of a record crosses the bus.
+ * PGPU_EINVAL (with a message): no run_meg since the last run; min_factor_len 0, above 2^24 or not the MEG stage's; the
+ * results of a resident plan were overwritten by the run of another one; fetch before run_candidates.  An empty plan is
+ * PGPU_OK.  A rerun gives the same bytes.  The buffers come from where the MEG stage's do. */
+int pgpu_pairing_plan_run_candidates(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_cand_params* params);
+uint64_t pgpu_pairing_plan_candidate_exons(const pgpu_pairing_plan* plan);   /* exons of the last run_candidates */
+/* out: n_pat results; exons: at least candidate_exons entries (PGPU_ENOSPC when exons_cap is smaller) */
+int pgpu_pairing_plan_fetch_candidates(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_cand_result* out,
+                                       pgpu_factor* exons, size_t exons_cap);
+/* HIP-event time of the last run_candidates (count + scan + write); 0 without timing */
+double pgpu_pairing_plan_candidates_ms(const pgpu_pairing_plan* plan);
+
+/* Index form: the same for a caller that holds records (fetched ones: a resident plan's results expire with the next
+ * chunk's run; or hand-made ones).  records: records_len bytes; rec_first[i] .. rec_first[i + 1] delimits record i
+ * (n + 1 offsets); out: n results; *n_exons: exons written.  Synchronous and batched like the other pgpu_index_*
+ * queries.
+ *  - PGPU_EINVAL for the whole call: a null pointer (no message); min_factor_len 0 or above 2^24; rec_first not
+ *    ascending or beyond records_len; a record that is not at a multiple of 4, or shorter than 16 bytes; and in a record
+ *    without either flag: one shorter than its header's counts need (16 + 12 n_vertices + 2 (n_vertices + 1) + n_edges);
+ *    n_vertices > 64; CSR offsets that are not ascending or go beyond n_edges; a target >= n_vertices; a source or sink
+ *    (by its p) whose t is not its p or whose l is not 200; any other vertex, a pairing, with p < 0, l < 0 or
+ *    p + l > 2^29, or whose t or t + l lies outside the sequence.  A flagged record is a bare header: nothing behind its
+ *    16 bytes is read.
+ *  - PGPU_ENOSPC, with the needed count in *n_exons and nothing written to out or exons, when exons_cap is too small.
+ *  - n == 0 is PGPU_OK (*n_exons = 0).  idx may be built or loaded. */
+int pgpu_index_candidates(pgpu_ctx* ctx, const pgpu_index* idx, const void* records, size_t records_len,
+                          const uint64_t* rec_first, size_t n, const pgpu_cand_params* params,
+                          pgpu_cand_result* out, pgpu_factor* exons, size_t exons_cap, size_t* n_exons);
+/* HIP-event time of the kernels of the calling thread's last pgpu_index_candidates on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_candidates_kernel_ms(void);
+
 /* page-locked host memory for the buffers handed to the fetch calls (a pageable destination
  * makes the runtime stage the copy); plain malloc'ed memory works too, slower */
 int pgpu_host_alloc(pgpu_ctx* ctx, size_t bytes, void** out);

@@ -102,6 +102,15 @@ class GapsResult(C.Structure):     # pgpu_gaps_result
     _fields_ = [("status", C.c_int32), ("verdict", C.c_uint32), ("total_edit", C.c_uint32), ("n_kept", C.c_uint32)]
 
 
+class CandParams(C.Structure):     # pgpu_cand_params
+    _fields_ = [("min_factor_len", C.c_uint32), ("min_intron_length", C.c_int32)]
+
+
+class CandResult(C.Structure):     # pgpu_cand_result
+    _fields_ = [("kind", C.c_uint32), ("work", C.c_uint32), ("first_exon", C.c_uint32), ("n_exons", C.c_uint16),
+                ("n_pairs", C.c_uint16)]
+
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -125,6 +134,10 @@ CLEAN_RESULT_DTYPE = [("status", "<i4"), ("verdict", "<u4"), ("first_kept", "<u4
 GAPS_MAX_EXONS, GAPS_MAX_EST_GAP, GAPS_MAX_ERRORS = 64, 64, 20
 GAPS_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u4"), ("reserved", "<u4")]
 GAPS_RESULT_DTYPE = [("status", "<i4"), ("verdict", "<u4"), ("total_edit", "<u4"), ("n_kept", "<u4")]
+CAND_NONE, CAND_NOT_PATH, CAND_REFUSED, CAND_ONE = range(4)
+MEG_TOO_COMPLEX, MEG_UNAVAILABLE = 1, 2
+CAND_PARAMS_DTYPE = [("min_factor_len", "<u4"), ("min_intron_length", "<i4")]
+CAND_RESULT_DTYPE = [("kind", "<u4"), ("work", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u2"), ("n_pairs", "<u2")]
 
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
@@ -138,6 +151,7 @@ assert C.sizeof(Factor) == 16 and C.sizeof(RefineQuery) == 96 and C.sizeof(Refin
 assert C.sizeof(ChainQuery) == 40 and C.sizeof(ChainResult) == 16
 assert C.sizeof(CleanQuery) == 32 and C.sizeof(CleanResult) == 16
 assert C.sizeof(GapsQuery) == 24 and C.sizeof(GapsResult) == 16
+assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -154,6 +168,8 @@ EXPORTS = [
     "pgpu_pairing_plan_destroy",
     "pgpu_pairing_plan_run_meg", "pgpu_pairing_plan_meg_bytes", "pgpu_pairing_plan_fetch_meg",
     "pgpu_pairing_plan_meg_ms", "pgpu_host_alloc", "pgpu_host_free",
+    "pgpu_pairing_plan_run_candidates", "pgpu_pairing_plan_candidate_exons", "pgpu_pairing_plan_fetch_candidates",
+    "pgpu_pairing_plan_candidates_ms", "pgpu_index_candidates", "pgpu_index_candidates_kernel_ms",
     "pgpu_comm_unique_id", "pgpu_comm_init", "pgpu_gather", "pgpu_allgather", "pgpu_comm_destroy",
     "pgpu_range_push", "pgpu_range_pop", "pgpu_build_info",
     "pgpu_dp_plan_create", "pgpu_dp_plan_create_parts", "pgpu_dp_plan_launch", "pgpu_dp_plan_sync",
@@ -227,6 +243,16 @@ def lib():
         L.pgpu_pairing_plan_meg_ms.argtypes = [vp]
         L.pgpu_pairing_plan_meg_ms.restype = C.c_double
         L.pgpu_pairing_plan_fetch_meg.argtypes = [vp, vp, vp, sz, C.POINTER(u64)]
+        L.pgpu_pairing_plan_run_candidates.argtypes = [vp, vp, C.POINTER(CandParams)]
+        L.pgpu_pairing_plan_candidate_exons.argtypes = [vp]
+        L.pgpu_pairing_plan_candidate_exons.restype = u64
+        L.pgpu_pairing_plan_fetch_candidates.argtypes = [vp, vp, C.POINTER(CandResult), C.POINTER(Factor), sz]
+        L.pgpu_pairing_plan_candidates_ms.argtypes = [vp]
+        L.pgpu_pairing_plan_candidates_ms.restype = C.c_double
+        L.pgpu_index_candidates.argtypes = [vp, vp, vp, sz, C.POINTER(u64), sz, C.POINTER(CandParams), C.POINTER(CandResult),
+                                            C.POINTER(Factor), sz, C.POINTER(sz)]
+        L.pgpu_index_candidates_kernel_ms.argtypes = []
+        L.pgpu_index_candidates_kernel_ms.restype = C.c_double
         L.pgpu_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.pgpu_host_free.argtypes = [vp, vp]
         L.pgpu_comm_unique_id.argtypes = [vp, vp]
@@ -494,6 +520,35 @@ class Index:
     def gap_chains_kernel_ms(self):
         return self.ctx.L.pgpu_index_gap_chains_kernel_ms()
 
+    def candidates_raw(self, records: bytes, rec_first, n: int, min_factor_len, min_intron_length, exons_cap: int):
+        """One pgpu_index_candidates call as it is: `records` the concatenated MEG records, `rec_first` a numpy uint64 array
+        of n + 1 offsets.  Returns (rc, results as a numpy array of CAND_RESULT_DTYPE, exons (exons_cap entries), n_exons)."""
+        import numpy as np
+        res = np.zeros(n, dtype=np.dtype(CAND_RESULT_DTYPE))
+        exons = np.zeros(exons_cap, dtype=np.dtype(FACTOR_DTYPE))
+        prm = CandParams(min_factor_len, min_intron_length)
+        total = C.c_size_t(0)
+        rc = self.ctx.L.pgpu_index_candidates(self.ctx.h, self.h, records, len(records), rec_first.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                              n, C.byref(prm), res.ctypes.data_as(C.POINTER(CandResult)),
+                                              exons.ctypes.data_as(C.POINTER(Factor)), exons_cap, C.byref(total))
+        return rc, res, exons, total.value
+
+    def candidates(self, records, min_factor_len=15, min_intron_length=40):
+        """The candidate factorization of every MEG record of the list `records` (bytes each, as PairingPlan.fetch_meg
+        returns them) that is one path: (results as a numpy array of CAND_RESULT_DTYPE, exons as one of FACTOR_DTYPE)."""
+        import numpy as np
+        first = np.zeros(len(records) + 1, dtype=np.uint64)
+        np.cumsum([len(r) for r in records], out=first[1:])
+        blob = b"".join(records)
+        rc, res, exons, total = self.candidates_raw(blob, first, len(records), min_factor_len, min_intron_length, 0)
+        if rc == PGPU_ENOSPC:
+            rc, res, exons, total = self.candidates_raw(blob, first, len(records), min_factor_len, min_intron_length, total)
+        self.ctx.check(rc)
+        return res, exons[:total]
+
+    def candidates_kernel_ms(self):
+        return self.ctx.L.pgpu_index_candidates_kernel_ms()
+
     def close(self):
         if self.h:
             self.ctx.L.pgpu_index_destroy(self.ctx.h, self.h)
@@ -579,6 +634,25 @@ class PairingPlan:
             self.ctx.h, self.h, out.ctypes.data_as(C.c_void_p), n, first.ctypes.data_as(C.POINTER(C.c_uint64))))
         raw = out.tobytes()
         return [raw[int(first[i]):int(first[i + 1])] for i in range(self.n_pat)]
+
+    def run_candidates(self, min_factor_len=15, min_intron_length=40):
+        """the candidate stage over the records of the last run_meg, which stay in HBM; returns the number of exons"""
+        prm = CandParams(min_factor_len, min_intron_length)
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_run_candidates(self.ctx.h, self.h, C.byref(prm)))
+        return self.ctx.L.pgpu_pairing_plan_candidate_exons(self.h)
+
+    def fetch_candidates(self):
+        """(results as a numpy array of CAND_RESULT_DTYPE, one per pattern; exons as one of FACTOR_DTYPE)"""
+        import numpy as np
+        n = self.ctx.L.pgpu_pairing_plan_candidate_exons(self.h)
+        res = np.zeros(self.n_pat, dtype=np.dtype(CAND_RESULT_DTYPE))
+        exons = np.zeros(n, dtype=np.dtype(FACTOR_DTYPE))
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_fetch_candidates(
+            self.ctx.h, self.h, res.ctypes.data_as(C.POINTER(CandResult)), exons.ctypes.data_as(C.POINTER(Factor)), n))
+        return res, exons
+
+    def candidates_ms(self):
+        return self.ctx.L.pgpu_pairing_plan_candidates_ms(self.h)
 
     def close(self):
         if self.h:

@@ -63,6 +63,13 @@ void pgpu_meg_launch_build(const pgpu_pairing* pairs, const unsigned long long* 
                            hipStream_t st);
 void pgpu_meg_launch_emit(uint32_t n_pat, const void* scratch, const void* info, const unsigned long long* rec_off,
                           uint8_t* out, hipStream_t st);
+// pgpu_cand.hip: the candidate factorization of every record of a batch of MEG records, in two launches around an exclusive
+// scan of `counts` (n + 1 entries, the last one 0): the count pass fills res and counts, the write pass first_exon and exons
+void pgpu_cand_launch_count(const uint8_t* recs, const unsigned long long* rec_first, uint32_t n, const uint8_t* T, uint32_t tlen,
+                            const pgpu_cand_params* prm, pgpu_cand_result* res, uint32_t* counts, hipStream_t st);
+void pgpu_cand_launch_write(const uint8_t* recs, const unsigned long long* rec_first, uint32_t n, const uint8_t* T, uint32_t tlen,
+                            const pgpu_cand_params* prm, pgpu_cand_result* res, const unsigned long long* first_exon,
+                            pgpu_factor* exons, hipStream_t st);
 // PGPU_TRACE_ALLOC=1: every page-locked host allocation of the library on stderr (size, address, call site)
 #include <cstdio>
 #include <cstdlib>

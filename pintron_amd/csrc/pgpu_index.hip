@@ -865,6 +865,17 @@ struct pgpu_pairing_plan {
   float meg_ms = 0.f;
   uint32_t last_L = 0;
   bool have_pairs = false;
+  // candidate stage (pgpu_cand.hip) over the records of the last run_meg
+  uint32_t meg_L = 0;
+  bool have_meg = false, have_cand = false;
+  pgpu_cand_result* d_cand_res = nullptr;
+  uint32_t* d_cand_cnt = nullptr;
+  unsigned long long* d_cand_first = nullptr;
+  pgpu_factor* d_cand_exons = nullptr;
+  size_t cand_exons_cap = 0;
+  unsigned long long cand_total = 0;
+  hipEvent_t cand_ev[2] = {nullptr, nullptr};
+  float cand_ms = 0.f;
 };
 
 // device buffer for a pairing plan: from the context's pool when the plan holds it
@@ -887,9 +898,11 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_cand_off); hipFree(p->d_out_off); hipFree(p->d_out_first); hipFree(p->d_cand);
     hipFree(p->d_keep); hipFree(p->d_out); hipFree(p->d_tmp);
     hipFree(p->d_meg_scratch); hipFree(p->d_meg_info); hipFree(p->d_meg_bytes); hipFree(p->d_meg_off); hipFree(p->d_meg_out);
+    hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->meg_ev) if (e) hipEventDestroy(e);
+  for (auto& e : p->cand_ev) if (e) hipEventDestroy(e);
   delete p;
 }
 
@@ -992,6 +1005,7 @@ extern "C" int pgpu_pairing_plan_run(pgpu_ctx* ctx, pgpu_pairing_plan* p, const 
   const dim3 pgrid((unsigned)(p->n_pat ? p->n_pat : 1)), pblk(64);
   p->n_cand = p->n_out = 0;
   p->have_pairs = false;
+  p->have_meg = p->have_cand = false;               // the records and candidates of the run before are gone with its pairings
   if (p->n_pat == 0) return PGPU_OK;
   if (p->resident) {
     pgpu_ctx_pool_set_owner(ctx, 1, p);               // whatever another resident plan left there is gone from here on
@@ -1049,6 +1063,7 @@ extern "C" int pgpu_pairing_plan_run_meg(pgpu_ctx* ctx, pgpu_pairing_plan* p, co
   if (!ctx || !p || !prm || prm->min_factor_len == 0) return PGPU_EINVAL;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   p->meg_total = 0; p->meg_ms = 0.f;
+  p->have_meg = p->have_cand = false;
   if (p->n_pat == 0) return PGPU_OK;
   if (!p->have_pairs || p->last_L != prm->min_factor_len)
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_meg needs the pairings of pgpu_pairing_plan_run with the same min_factor_len");
@@ -1084,6 +1099,7 @@ extern "C" int pgpu_pairing_plan_run_meg(pgpu_ctx* ctx, pgpu_pairing_plan* p, co
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
   if (p->meg_ev[0]) hipEventElapsedTime(&p->meg_ms, p->meg_ev[0], p->meg_ev[1]);
+  p->have_meg = true; p->meg_L = prm->min_factor_len;
 done:
   return rc;
 }
@@ -1102,6 +1118,76 @@ extern "C" int pgpu_pairing_plan_fetch_meg(pgpu_ctx* ctx, pgpu_pairing_plan* p, 
   if (p->n_pat == 0) { rec_first[0] = 0; return PGPU_OK; }
   if (p->meg_total) TRY_HIP(hipMemcpyAsync(out, p->d_meg_out, (size_t)p->meg_total, hipMemcpyDeviceToHost, st));
   TRY_HIP(hipMemcpyAsync(rec_first, p->d_meg_off, (p->n_pat + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  TRY_HIP(pgpu_ctx_wait(ctx));
+done:
+  return rc;
+}
+
+// the candidate factorization of every record that pgpu_pairing_plan_run_meg left in HBM (pgpu_cand.hip)
+extern "C" int pgpu_pairing_plan_run_candidates(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_cand_params* prm) {
+  if (!ctx || !p || !prm) return PGPU_EINVAL;
+  p->cand_total = 0; p->cand_ms = 0.f; p->have_cand = false;
+  if (prm->min_factor_len == 0 || prm->min_factor_len > (1u << 24))
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad candidate parameters (min_factor_len 0 or above 2^24)");
+  if (p->n_pat == 0) { p->have_cand = true; return PGPU_OK; }
+  if (!p->have_meg || p->meg_L != prm->min_factor_len)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_candidates needs the records of pgpu_pairing_plan_run_meg with the same min_factor_len");
+  if (p->resident && pgpu_ctx_pool_owner(ctx, 1) != p)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "the records of this resident plan were overwritten by the run of another one");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  if (p->resident) { p->d_cand_res = nullptr; p->d_cand_exons = nullptr; }     // taken anew: the pool may have moved
+  int rc = PGPU_OK;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  const uint32_t np = (uint32_t)p->n_pat;
+  const pgpu_index* ix = p->idx;
+  pgpu_range_push("candidates");
+  struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
+  if (!p->d_cand_res) {
+    NEED(p->d_cand_res = plan_alloc<pgpu_cand_result>(p, 23, np));
+    NEED(p->d_cand_cnt = plan_alloc<uint32_t>(p, 24, (size_t)np + 1));
+    NEED(p->d_cand_first = plan_alloc<unsigned long long>(p, 25, (size_t)np + 1));
+    if (pgpu_ctx_timing(ctx) && !p->cand_ev[0]) for (auto& e : p->cand_ev) TRY_HIP(hipEventCreate(&e));
+  }
+  if (p->cand_ev[0]) TRY_HIP(hipEventRecord(p->cand_ev[0], st));
+  pgpu_cand_launch_count(p->d_meg_out, p->d_meg_off, np, ix->d_gen, (uint32_t)ix->len, prm, p->d_cand_res, p->d_cand_cnt, st);
+  TRY_HIP(hipMemsetAsync(p->d_cand_cnt + np, 0, sizeof(uint32_t), st));
+  pgpu_exclusive_scan_u32(p->d_cand_cnt, p->d_cand_first, (size_t)np + 1, p->d_tmp, st);
+  TRY_HIP(hipMemcpyAsync(&p->cand_total, p->d_cand_first + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  TRY_HIP(pgpu_ctx_wait(ctx));
+  if (p->cand_total > p->cand_exons_cap || !p->d_cand_exons) {
+    if (!p->pooled) hipFree(p->d_cand_exons);
+    p->d_cand_exons = nullptr;
+    p->cand_exons_cap = (size_t)(p->cand_total + p->cand_total / 8 + 256);
+    NEED(p->d_cand_exons = plan_alloc<pgpu_factor>(p, 26, p->cand_exons_cap));
+  }
+  pgpu_cand_launch_write(p->d_meg_out, p->d_meg_off, np, ix->d_gen, (uint32_t)ix->len, prm, p->d_cand_res, p->d_cand_first,
+                         p->d_cand_exons, st);
+  if (p->cand_ev[1]) TRY_HIP(hipEventRecord(p->cand_ev[1], st));
+  TRY_HIP(pgpu_ctx_wait(ctx));
+  TRY_HIP(hipGetLastError());
+  if (p->cand_ev[0]) hipEventElapsedTime(&p->cand_ms, p->cand_ev[0], p->cand_ev[1]);
+  p->have_cand = true;
+done:
+  if (rc != PGPU_OK) p->cand_total = 0;
+  return rc;
+}
+
+extern "C" uint64_t pgpu_pairing_plan_candidate_exons(const pgpu_pairing_plan* p) { return p ? p->cand_total : 0; }
+extern "C" double pgpu_pairing_plan_candidates_ms(const pgpu_pairing_plan* p) { return p ? p->cand_ms : 0.0; }
+
+extern "C" int pgpu_pairing_plan_fetch_candidates(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_cand_result* out, pgpu_factor* exons,
+                                                  size_t exons_cap) {
+  if (!ctx || !p || (p->n_pat && !out) || (exons_cap && !exons)) return PGPU_EINVAL;
+  if (!p->have_cand) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_candidates needs pgpu_pairing_plan_run_candidates first");
+  if (p->resident && p->n_pat && pgpu_ctx_pool_owner(ctx, 1) != p)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "the results of this resident plan were overwritten by the run of another one");
+  if (exons_cap < p->cand_total) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  int rc = PGPU_OK;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_pat == 0) return PGPU_OK;
+  TRY_HIP(hipMemcpyAsync(out, p->d_cand_res, p->n_pat * sizeof(pgpu_cand_result), hipMemcpyDeviceToHost, st));
+  if (p->cand_total) TRY_HIP(hipMemcpyAsync(exons, p->d_cand_exons, (size_t)p->cand_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
   TRY_HIP(pgpu_ctx_wait(ctx));
 done:
   return rc;

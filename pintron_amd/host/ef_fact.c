@@ -981,6 +981,37 @@ static bool chain_embedding(const void* rec, const ef_config* cfg, const char* G
   return true;
 }
 
+/* The candidate of one MEG record as pgpu_pairing_plan_run_candidates / pgpu_index_candidates define it
+ * (include/pintron_gpu.h): chain_embedding and factorizations_from_embeddings above, with the list flattened into
+ * out_exons (at most cap entries are written; *n_exons is the number there are).  Returns the kind: 0 the record is
+ * flagged, 1 not one path, 2 update_embedding refused, 3 one candidate.  *work is what chain_embedding charged, with no
+ * budget to compare it with: that stays with the caller, as it does on the device. */
+unsigned ef_chain_candidate(const void* rec, const ef_config* cfg, const char* GEN, ef_factor* out_exons, size_t cap,
+                            unsigned* n_exons, unsigned* n_pairs, unsigned* work) {
+  *n_exons = 0; *n_pairs = 0; *work = 0;
+  if (((const uint32_t*)rec)[2] & 3u) return 0;
+  ef_work wk = { 0, ~0ull };
+  emb* chain = NULL;
+  if (!chain_embedding(rec, cfg, GEN, &wk, &chain)) return 1;
+  *work = (unsigned)wk.used;
+  if (!chain) return 2;
+  *n_pairs = chain->n;
+  ef_list* embs = efl_new();
+  efl_push_back(embs, chain);
+  ef_list* cands = factorizations_from_embeddings(embs, cfg);
+  efl_free(embs, embedding_free);
+  ef_list* fact = (ef_list*)efl_head(cands);
+  ef_iter it = efl_begin(fact);
+  while (efi_has_next(&it)) {
+    const ef_factor* x = (const ef_factor*)efi_next(&it);
+    if (*n_exons < cap) out_exons[*n_exons] = *x;
+    ++*n_exons;
+  }
+  ef_factorization_free(fact);
+  efl_free(cands, NULL);
+  return 3;
+}
+
 ef_est* ef_get_est_factorizations(const ef_seq* est_info, ef_meg* V, const ef_config* cfg,
                                   const ef_seq* gen_info, ef_backend* be) {
   ef_phase(EFP_EMBED);

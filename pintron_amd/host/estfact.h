@@ -411,6 +411,10 @@ extern int ef_ahead_on;            /* PINTRON_AHEAD=0 switches the asking ahead 
 
 /* ---- factorizations (include/types.h:160-180) ------------------------------------------------ */
 typedef struct { int EST_start, EST_end, GEN_start, GEN_end; } ef_factor;   /* 0-based inclusive */
+/* the candidate of one MEG record (layout: include/pintron_gpu.h) that is one path: kind 0 flagged, 1 not a path, 2 refused,
+ * 3 one candidate with its exons, the embedding's length and the work units charged (ef_fact.c) */
+unsigned ef_chain_candidate(const void* rec, const ef_config* cfg, const char* GEN, ef_factor* out_exons, size_t cap,
+                            unsigned* n_exons, unsigned* n_pairs, unsigned* work);
 /* a factorization = ef_list of ef_factor*; a list of factorizations = ef_list of ef_list* */
 
 typedef struct {
