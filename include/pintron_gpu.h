@@ -613,6 +613,95 @@ int pgpu_index_candidates(pgpu_ctx* ctx, const pgpu_index* idx, const void* reco
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_candidates_kernel_ms(void);
 
+/* ------------------------------------------------------------------------------------------ */
+/* factorizations -- a candidate taken through the cleaning steps (pgpu_index_clean_chains),   */
+/* check_gap_errors (pgpu_index_gap_chains) and the refinement loop (pgpu_index_refine_chains)  */
+/* in ONE call, nothing leaving HBM in between: for an EST with exactly one candidate this is   */
+/* all that get_EST_factorizations (src/est-factorizations.c) does between the graph and        */
+/* correct_tail -- FILTER 1 and FILTER 3 compare a candidate with the best one and are no-ops   */
+/* on one (max_cov - c == 0, g - min_gl == 0); max_number_of_factorizations stays with the      */
+/* caller.  The three stage kernels are the ones of the chained entries; between them one       */
+/* thread per EST does what a caller of those entries does on the host: cut the kept run out of */
+/* clean's answer, drop the exons gaps merged, build the next query.                            */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  double  complexity_threshold;       /* clean: config->complexity_threshold */
+  int32_t suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen;   /* refine: each in [0, 2^24] */
+  int32_t min_intron_length;          /* refine: config->min_intron_length; only compared: any value */
+} pgpu_fact_params;          /* 24 bytes: 0, 8, 12, 16, 20; no padding */
+
+#define PGPU_FACT_HOST  0u   /* no answer from the device: the caller runs its own path from the MEG record */
+#define PGPU_FACT_EMPTY 1u   /* the answer is "no factorization" */
+#define PGPU_FACT_DONE  2u   /* exons[first_exon .. first_exon + n_exons): the factorization as the loop of
+                                est-factorizations.c:446-490 leaves it, the first-exon rule (:476-485) applied */
+typedef struct {
+  uint8_t  outcome;          /* PGPU_FACT_* */
+  uint8_t  stage;            /* where the outcome fell: 0 candidate, 1 clean, 2 gaps, 3 refine */
+  uint16_t detail;           /* HOST: at stage 0 the candidate's kind (PGPU_CAND_NONE, PGPU_CAND_NOT_PATH); at stages 1-3:
+                                1 a cap (that entry's PGPU_ERANGE for the query), 2 an input that entry's validator refuses
+                                (for a whole call, there; for this EST alone, here).
+                                EMPTY: at stage 0 PGPU_CAND_REFUSED; at stage 1 clean's verdict 1 .. 7; at stage 2: 1.
+                                DONE: bit 0 = dropped_first of pgpu_chain_result (the exon is not among the n_exons) */
+  uint32_t first_exon;       /* DONE only, else 0: into the call's compact exon array */
+  uint16_t n_exons;          /* DONE only (>= 1), else 0 */
+  uint16_t n_merged;         /* DONE only, else 0: exons check_gap_errors merged into the one before them */
+  uint32_t total_edit;       /* tot_out_edit_distance of check_gap_errors whenever the gaps stage answered (EMPTY at stage 2,
+                                every outcome at stage 3); else 0 */
+} pgpu_fact_result;          /* 16 bytes: outcome 0, stage 1, detail 2, first_exon 4, n_exons 8, n_merged 10, total_edit 12 */
+
+/*  - The stages, per EST, each exactly the chained entry of that name on a query of its own:
+ *    0. the candidate: none (HOST, detail = the kind), refused by update_embedding (EMPTY), or one list of exons;
+ *    1. clean with complexity_threshold.  What pgpu_index_clean_chains refuses for a whole call is HOST with detail 2 for
+ *       this EST: an exon coordinate outside [-1, est_len] / [-1, length of the sequence], an empty EST, or, for a list that
+ *       passes step 1, an end exon that begins in front of or ends behind its string.  PGPU_ERANGE is HOST with detail 1,
+ *       verdict 1 .. 7 is EMPTY (also 7, whose kept run the chained entry reports: there is no factorization);
+ *    2. gaps on the kept run [first_kept, first_kept + n_kept) of clean's out_exons.  Two adjacent exons out of order on
+ *       either string or an EST gap longer than its genomic gap: HOST, detail 2.  PGPU_ERANGE: HOST, detail 1.  Verdict 1:
+ *       EMPTY, detail 1;
+ *    3. refine on the exons gaps kept (out_steps without bit 7), donors with their merged ends, with the four settings of
+ *       the call.  Two adjacent exons not strictly in order: HOST, detail 2.  PGPU_ERANGE: HOST, detail 1 (the partly
+ *       refined chain is not reported).  Otherwise DONE: the chain's out_exons, less the first one when dropped_first.
+ *  - exons and steps of a call are compact, in EST order; only DONE has any.  steps[k] is pgpu_index_refine_chains'
+ *    out_steps of that exon: path in bits 0-3, refined in bit 7, for the intron in front of it; 0 for the first exon of the
+ *    chain (after dropped_first the list begins with the chain's second exon, which keeps its byte).
+ *  - An outcome never depends on another EST of the call: an EST with nothing to do at a stage is given that stage's
+ *    trivial query (clean: one exon with EST_start = -1; gaps and refine: one exon) on a placeholder exon of its own.
+ *  - Comparing pgpu_cand_result.work with a budget stays with the caller, as for the candidate stage. */
+
+/* Plan form: the candidates of the last pgpu_pairing_plan_run_candidates, where they lie; the ESTs are the plan's patterns.
+ * ONE goes down the chain, REFUSED is EMPTY at stage 0, NONE and NOT_PATH are HOST at stage 0.  The candidates stay
+ * fetchable and unchanged.  PGPU_EINVAL (with a message): no run_candidates since the last run or run_meg; the results of
+ * a resident plan were overwritten by the run of another one; a suffpref length outside [0, 2^24]; more than 2^31 - 1
+ * patterns or candidate exons (as the index form); fetch before run_factorizations.  An empty plan is PGPU_OK.  A rerun
+ * gives the same bytes.  The buffers come from where the MEG stage's do.  One host wait lies inside the call (8 bytes: the
+ * workspace the end-exon alignments of clean need). */
+int pgpu_pairing_plan_run_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_fact_params* params);
+uint64_t pgpu_pairing_plan_factorization_exons(const pgpu_pairing_plan* plan);   /* exons of the last run_factorizations */
+/* out: n_pat results; exons, steps: at least factorization_exons entries (PGPU_ENOSPC when cap is smaller) */
+int pgpu_pairing_plan_fetch_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_fact_result* out, pgpu_factor* exons,
+                                           uint8_t* steps, size_t cap);
+/* HIP-event times of the last run_factorizations: k = 0 the whole call (hand-off kernels, the host wait, the scan
+ * included), 1 clean_kernel, 2 gaps_kernel, 3 chain_kernel; 0 without timing */
+double pgpu_pairing_plan_factorizations_ms(const pgpu_pairing_plan* plan, int k);
+
+/* Index form: the same driver for a caller that holds candidates (fetched ones, or hand-made ones).  One query = one EST:
+ * the fields of pgpu_gaps_query, where n_exons == 0 means "no candidate" (HOST at stage 0, detail PGPU_CAND_NONE; first_exon
+ * is then not looked at).  out: n results; out_exons, out_steps: cap entries; *n_out: exons written.  One upload, one
+ * download; synchronous and batched like the other pgpu_index_* queries.
+ *  - PGPU_EINVAL for the whole call only for structure: a null pointer (no message); est_off + est_len > ests_len or
+ *    first_exon + n_exons > n_exons_total; est_len == 0 or > 2^31 - 1; reserved != 0; two queries share an exon; a suffpref
+ *    length outside [0, 2^24]; more than 2^31 - 1 queries or exons.  Whatever concerns the VALUES of the exons, factor
+ *    coordinates outside their strings included, is HOST with detail 2 for that query, exactly as in the plan form.
+ *  - PGPU_ENOSPC, with the needed count in *n_out and nothing written to out, out_exons or out_steps, when cap is too small.
+ *  - n == 0 is PGPU_OK (*n_out = 0).  idx may be built or loaded. */
+typedef pgpu_gaps_query pgpu_fact_query;     /* 24 bytes */
+int pgpu_index_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len, const pgpu_factor* exons,
+                              size_t n_exons_total, const pgpu_fact_query* q, size_t n, const pgpu_fact_params* params,
+                              pgpu_fact_result* out, pgpu_factor* out_exons, uint8_t* out_steps, size_t cap, size_t* n_out);
+/* HIP-event time of the whole device part of the calling thread's last pgpu_index_factorizations on a context with timing
+ * on (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_factorizations_kernel_ms(void);
+
 /* page-locked host memory for the buffers handed to the fetch calls (a pageable destination
  * makes the runtime stage the copy); plain malloc'ed memory works too, slower */
 int pgpu_host_alloc(pgpu_ctx* ctx, size_t bytes, void** out);

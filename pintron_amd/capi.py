@@ -111,6 +111,18 @@ class CandResult(C.Structure):     # pgpu_cand_result
                 ("n_pairs", C.c_uint16)]
 
 
+class FactParams(C.Structure):     # pgpu_fact_params
+    _fields_ = [("complexity_threshold", C.c_double), ("suffpref_length_on_est", C.c_int32),
+                ("suffpref_length_for_intron", C.c_int32), ("suffpref_length_on_gen", C.c_int32), ("min_intron_length", C.c_int32)]
+
+
+class FactResult(C.Structure):     # pgpu_fact_result
+    _fields_ = [("outcome", C.c_uint8), ("stage", C.c_uint8), ("detail", C.c_uint16), ("first_exon", C.c_uint32),
+                ("n_exons", C.c_uint16), ("n_merged", C.c_uint16), ("total_edit", C.c_uint32)]
+
+
+FactQuery = GapsQuery              # pgpu_fact_query: n_exons == 0 is "no candidate"
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -138,6 +150,12 @@ CAND_NONE, CAND_NOT_PATH, CAND_REFUSED, CAND_ONE = range(4)
 MEG_TOO_COMPLEX, MEG_UNAVAILABLE = 1, 2
 CAND_PARAMS_DTYPE = [("min_factor_len", "<u4"), ("min_intron_length", "<i4")]
 CAND_RESULT_DTYPE = [("kind", "<u4"), ("work", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u2"), ("n_pairs", "<u2")]
+FACT_HOST, FACT_EMPTY, FACT_DONE = range(3)
+FACT_PARAMS_DTYPE = [("complexity_threshold", "<f8"), ("suffpref_length_on_est", "<i4"), ("suffpref_length_for_intron", "<i4"),
+                     ("suffpref_length_on_gen", "<i4"), ("min_intron_length", "<i4")]
+FACT_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("first_exon", "<u4"), ("n_exons", "<u2"),
+                     ("n_merged", "<u2"), ("total_edit", "<u4")]
+FACT_QUERY_DTYPE = GAPS_QUERY_DTYPE
 
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
@@ -152,6 +170,7 @@ assert C.sizeof(ChainQuery) == 40 and C.sizeof(ChainResult) == 16
 assert C.sizeof(CleanQuery) == 32 and C.sizeof(CleanResult) == 16
 assert C.sizeof(GapsQuery) == 24 and C.sizeof(GapsResult) == 16
 assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
+assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -170,6 +189,8 @@ EXPORTS = [
     "pgpu_pairing_plan_meg_ms", "pgpu_host_alloc", "pgpu_host_free",
     "pgpu_pairing_plan_run_candidates", "pgpu_pairing_plan_candidate_exons", "pgpu_pairing_plan_fetch_candidates",
     "pgpu_pairing_plan_candidates_ms", "pgpu_index_candidates", "pgpu_index_candidates_kernel_ms",
+    "pgpu_pairing_plan_run_factorizations", "pgpu_pairing_plan_factorization_exons", "pgpu_pairing_plan_fetch_factorizations",
+    "pgpu_pairing_plan_factorizations_ms", "pgpu_index_factorizations", "pgpu_index_factorizations_kernel_ms",
     "pgpu_comm_unique_id", "pgpu_comm_init", "pgpu_gather", "pgpu_allgather", "pgpu_comm_destroy",
     "pgpu_range_push", "pgpu_range_pop", "pgpu_build_info",
     "pgpu_dp_plan_create", "pgpu_dp_plan_create_parts", "pgpu_dp_plan_launch", "pgpu_dp_plan_sync",
@@ -253,6 +274,18 @@ def lib():
                                             C.POINTER(Factor), sz, C.POINTER(sz)]
         L.pgpu_index_candidates_kernel_ms.argtypes = []
         L.pgpu_index_candidates_kernel_ms.restype = C.c_double
+        L.pgpu_pairing_plan_run_factorizations.argtypes = [vp, vp, C.POINTER(FactParams)]
+        L.pgpu_pairing_plan_factorization_exons.argtypes = [vp]
+        L.pgpu_pairing_plan_factorization_exons.restype = u64
+        L.pgpu_pairing_plan_fetch_factorizations.argtypes = [vp, vp, C.POINTER(FactResult), C.POINTER(Factor),
+                                                             C.POINTER(C.c_uint8), sz]
+        L.pgpu_pairing_plan_factorizations_ms.argtypes = [vp, C.c_int]
+        L.pgpu_pairing_plan_factorizations_ms.restype = C.c_double
+        L.pgpu_index_factorizations.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(FactQuery), sz,
+                                                C.POINTER(FactParams), C.POINTER(FactResult), C.POINTER(Factor),
+                                                C.POINTER(C.c_uint8), sz, C.POINTER(sz)]
+        L.pgpu_index_factorizations_kernel_ms.argtypes = []
+        L.pgpu_index_factorizations_kernel_ms.restype = C.c_double
         L.pgpu_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.pgpu_host_free.argtypes = [vp, vp]
         L.pgpu_comm_unique_id.argtypes = [vp, vp]
@@ -549,6 +582,34 @@ class Index:
     def candidates_kernel_ms(self):
         return self.ctx.L.pgpu_index_candidates_kernel_ms()
 
+    def factorizations_raw(self, ests: bytes, exons, queries, n: int, params, cap: int):
+        """One pgpu_index_factorizations call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+        FACT_QUERY_DTYPE, `params` a FactParams.  Returns (rc, results as a numpy array of FACT_RESULT_DTYPE, exons and step
+        bytes (cap entries each), n_out)."""
+        import numpy as np
+        res = np.zeros(n, dtype=np.dtype(FACT_RESULT_DTYPE))
+        out_exons = np.zeros(cap, dtype=np.dtype(FACTOR_DTYPE))
+        out_steps = np.zeros(cap, dtype=np.uint8)
+        total = C.c_size_t(0)
+        rc = self.ctx.L.pgpu_index_factorizations(
+            self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)), len(exons),
+            queries.ctypes.data_as(C.POINTER(FactQuery)), n, C.byref(params), res.ctypes.data_as(C.POINTER(FactResult)),
+            out_exons.ctypes.data_as(C.POINTER(Factor)), out_steps.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(total))
+        return rc, res, out_exons, out_steps, total.value
+
+    def factorizations(self, ests: bytes, exons, queries, complexity_threshold=20.0, suffpref_length_on_est=30,
+                       suffpref_length_for_intron=70, suffpref_length_on_gen=30, min_intron_length=40):
+        """Every candidate `queries` names through clean, gaps and refine in one call (n_exons == 0: no candidate):
+        (results as a numpy array of FACT_RESULT_DTYPE, the final exons, compact, and their step bytes)."""
+        prm = FactParams(complexity_threshold, suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen,
+                         min_intron_length)
+        rc, res, out_exons, out_steps, total = self.factorizations_raw(ests, exons, queries, len(queries), prm, len(exons))
+        self.ctx.check(rc)
+        return res, out_exons[:total], out_steps[:total]
+
+    def factorizations_kernel_ms(self):
+        return self.ctx.L.pgpu_index_factorizations_kernel_ms()
+
     def close(self):
         if self.h:
             self.ctx.L.pgpu_index_destroy(self.ctx.h, self.h)
@@ -653,6 +714,31 @@ class PairingPlan:
 
     def candidates_ms(self):
         return self.ctx.L.pgpu_pairing_plan_candidates_ms(self.h)
+
+    def run_factorizations(self, complexity_threshold=20.0, suffpref_length_on_est=30, suffpref_length_for_intron=70,
+                           suffpref_length_on_gen=30, min_intron_length=40):
+        """every candidate of the last run_candidates through clean, gaps and refine, where it lies; returns the number of
+        exons of the answer"""
+        prm = FactParams(complexity_threshold, suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen,
+                         min_intron_length)
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_run_factorizations(self.ctx.h, self.h, C.byref(prm)))
+        return self.ctx.L.pgpu_pairing_plan_factorization_exons(self.h)
+
+    def fetch_factorizations(self):
+        """(results as a numpy array of FACT_RESULT_DTYPE, one per pattern; the final exons, compact; their step bytes)"""
+        import numpy as np
+        n = self.ctx.L.pgpu_pairing_plan_factorization_exons(self.h)
+        res = np.zeros(self.n_pat, dtype=np.dtype(FACT_RESULT_DTYPE))
+        exons = np.zeros(n, dtype=np.dtype(FACTOR_DTYPE))
+        steps = np.zeros(n, dtype=np.uint8)
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_fetch_factorizations(
+            self.ctx.h, self.h, res.ctypes.data_as(C.POINTER(FactResult)), exons.ctypes.data_as(C.POINTER(Factor)),
+            steps.ctypes.data_as(C.POINTER(C.c_uint8)), n))
+        return res, exons, steps
+
+    def factorizations_ms(self, k=0):
+        """HIP-event time of the last run_factorizations: k = 0 the whole call, 1 clean, 2 gaps, 3 refine"""
+        return self.ctx.L.pgpu_pairing_plan_factorizations_ms(self.h, k)
 
     def close(self):
         if self.h:

@@ -18,7 +18,7 @@
 // round, and hipMalloc/hipFree (the latter synchronises the device) would dominate.  A context
 // keeps one grow-only set of buffers per plan type; a plan borrows the set when it is free.
 struct BufPool {
-  static constexpr int SLOTS = 28;
+  static constexpr int SLOTS = 29;
   void* ptr[SLOTS] = {nullptr};
   size_t cap[SLOTS] = {0};
   bool busy = false;

@@ -21,6 +21,7 @@
 #include "pgpu_query_call.h"
 #include "pgpu_wave_dp.h"
 #include "pgpu_refine_body.h"
+#include "pgpu_stage_launch.h"
 
 namespace {
 
@@ -162,6 +163,14 @@ thread_local double t_chain_ms = 0.0;
 
 }  // namespace
 
+size_t pgpu_chain_ws_wave(void) { return WS_WAVE; }
+
+void pgpu_chain_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, const pgpu_factor* exons, const pgpu_chain_query* q,
+                       uint32_t n, uint8_t* ws, size_t waves, pgpu_factor* out_exons, uint8_t* out_steps, pgpu_chain_result* out,
+                       hipStream_t st) {
+  hipLaunchKernelGGL(chain_kernel, dim3((unsigned)waves), dim3(64), 0, st, T, tlen, ests, exons, q, n, ws, out_exons, out_steps, out);
+}
+
 extern "C" double pgpu_index_refine_chains_kernel_ms(void) { return t_chain_ms; }
 
 extern "C" int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
@@ -193,10 +202,9 @@ extern "C" int pgpu_index_refine_chains(pgpu_ctx* ctx, const pgpu_index* idx, co
   TRY_HIP(call.timing_events(1));
   TRY_HIP(chained_upload(call, L, ests, exons, q));
   TRY_HIP(call.record(0));
-  hipLaunchKernelGGL(chain_kernel, dim3((unsigned)waves), dim3(64), 0, call.st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
-                     (const pgpu_factor*)(call.d + L.exons), (const pgpu_chain_query*)(call.d + L.queries), (uint32_t)n,
-                     call.d + L.ws, (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes,
-                     (pgpu_chain_result*)(call.d + L.results));
+  pgpu_chain_launch(pgpu_index_genomic(idx), (uint32_t)glen, call.d, (const pgpu_factor*)(call.d + L.exons),
+                    (const pgpu_chain_query*)(call.d + L.queries), (uint32_t)n, call.d + L.ws, waves,
+                    (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes, (pgpu_chain_result*)(call.d + L.results), call.st);
   TRY_HIP(call.record(1));
   TRY_HIP(chained_download(call, L, out_exons, out_steps, out));
   TRY_HIP(pgpu_ctx_wait(ctx));

@@ -23,6 +23,7 @@
 #include "pgpu_internal.h"
 #include "pgpu_query_call.h"
 #include "pgpu_wave_dp.h"
+#include "pgpu_stage_launch.h"
 
 namespace {
 
@@ -32,11 +33,8 @@ constexpr uint32_t MAX_KBAND = 31;                     // 2k + 1 <= 64 diagonals
 static_assert(MAX_EXONS == 64, "one lane per exon, one ballot bit per exon");
 static_assert(ALIGN_BAND_K == MAX_KBAND, "both bands take the whole wave");
 
-// direction bytes of one end-exon alignment, as the plan builder sizes them: lev_wave<ALIGN> [step][64 lanes] of 1 B,
-// align_band [row / 16][64 lanes] of 4 B
-__host__ __device__ inline size_t dirs_wave(uint32_t lb) { return ((size_t)lb + 64) * 64; }
-__host__ __device__ inline size_t dirs_band(uint32_t la) { return ((size_t)(la >> 4) + 1) * 256; }
-__host__ __device__ inline size_t rows_bytes(uint32_t la, uint32_t lb) { return (2 * ((size_t)la + lb + 1) + 15) & ~(size_t)15; }
+// (dirs_wave, dirs_band, rows_bytes -- the direction bytes and the two rows of one end-exon alignment -- are in
+// pgpu_stage_launch.h, with the rule that sizes the workspace from them)
 
 struct CleanLds {
   __attribute__((aligned(16))) uint8_t win[TB_WIN_BYTES];   // the traceback's direction window ...
@@ -305,18 +303,29 @@ thread_local double t_clean_ms = 0.0;
 
 constexpr size_t WS_BUDGET = (size_t)256 << 20;      // bytes of per-wave workspace a call allocates at the most (see the grid)
 
-// what step 1 says of a query, on the host: the coordinate rules that follow hold for the queries that pass it
-bool passes_step1(const pgpu_factor* ex, uint32_t ne, uint32_t est_len) {
-  if (ne == 1 && (ex[0].EST_start < 0 || (uint32_t)ex[0].EST_start >= est_len)) return false;
-  int pe = -1, pg = -1;
-  for (uint32_t k = 0; k < ne; ++k) {
-    if (ex[k].EST_start > ex[k].EST_end || ex[k].GEN_start > ex[k].GEN_end || ex[k].EST_start < pe || ex[k].GEN_start < pg) return false;
-    pe = ex[k].EST_end; pg = ex[k].GEN_end;
+}  // namespace
+
+// the grid: 16 waves per compute unit, fewer where one long end exon has made the workspace of a wave large (266 KB for
+// 4096 genomic bytes under lev_wave<ALIGN>): the workspaces together stay within WS_BUDGET, at one wave per compute
+// unit at the least, so that one such query costs the batch some parallelism and not an allocation of a gigabyte
+hipError_t pgpu_clean_grid(size_t n, size_t ws_dirs, size_t ws_rows, size_t& waves, size_t& ws_wave) {
+  ws_wave = (ws_dirs + ws_rows + sizeof(DevResult) + 255) & ~(size_t)255;      // as clean_kernel lays it out
+  size_t cus = 0;
+  const hipError_t e = chained_waves(n, waves, cus);
+  if (e != hipSuccess) return e;
+  if (waves * ws_wave > WS_BUDGET) {
+    const size_t fit = WS_BUDGET / ws_wave > cus ? WS_BUDGET / ws_wave : cus;
+    if (waves > fit) waves = fit;
   }
-  return true;
+  return hipSuccess;
 }
 
-}  // namespace
+void pgpu_clean_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, const pgpu_factor* exons, const pgpu_clean_query* q,
+                       uint32_t n, uint8_t* ws, size_t ws_dirs, size_t ws_rows, size_t waves, pgpu_factor* out_exons,
+                       uint8_t* out_marks, pgpu_clean_result* out, uint32_t* undersized, hipStream_t st) {
+  hipLaunchKernelGGL(clean_kernel, dim3((unsigned)waves), dim3(64), 0, st, T, tlen, ests, exons, q, n, ws, ws_dirs, ws_rows, out_exons,
+                     out_marks, out, undersized);
+}
 
 extern "C" double pgpu_index_clean_chains_kernel_ms(void) { return t_clean_ms; }
 
@@ -330,26 +339,9 @@ extern "C" int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, con
   if (begun != CHAINED_GO) return begun;
   const size_t glen = pgpu_index_length(idx);
   // the workspace of one wave holds the longest end-exon alignment of the call (trimming only shortens an exon)
-  size_t ws_dirs = 256, ws_rows = 16;
-  // a clean query's own rules: an EST of at least one byte, and for what passes step 1 the my_asserts of :2140-2141 and
-  // :2199-2200 on its end exons -- which, in the same pass, size the workspace
+  size_t ws_dirs = CLEAN_WS_DIRS_MIN, ws_rows = CLEAN_WS_ROWS_MIN;
   const auto own = [&](const pgpu_clean_query& x, const pgpu_factor* ex) {
-    if (x.est_len == 0) return false;
-    if (!passes_step1(ex, x.n_exons, x.est_len)) return true;
-    const pgpu_factor& head = ex[0];
-    const pgpu_factor& tail = ex[x.n_exons - 1];
-    if (head.EST_start < 0 || head.GEN_start < 0 || (uint32_t)tail.EST_end >= x.est_len || (size_t)tail.GEN_end >= glen) return false;
-    if (x.n_exons > PGPU_CLEAN_MAX_EXONS) return true;                                    // refused on the device
-    for (const pgpu_factor* f : { &head, &tail }) {
-      const uint32_t la = (uint32_t)(f->EST_end - f->EST_start + 1), lb = (uint32_t)(f->GEN_end - f->GEN_start + 1);
-      if (la > PGPU_CLEAN_MAX_END_EXON || lb > PGPU_CLEAN_MAX_END_EXON) continue;      // refused on the device
-      const size_t d = la <= 64u ? dirs_wave(lb) : dirs_band(la);
-      if (d > ws_dirs) ws_dirs = d;
-      // (a single exon is aligned again as the head step trimmed it: to 64 EST bytes or fewer, lev_wave<ALIGN> takes it)
-      if (x.n_exons == 1 && la > 64u && dirs_wave(lb) > ws_dirs) ws_dirs = dirs_wave(lb);
-      if (rows_bytes(la, lb) > ws_rows) ws_rows = rows_bytes(la, lb);
-    }
-    return true;
+    return clean_query_need(ex, x.n_exons, x.est_len, glen, ws_dirs, ws_rows);
   };
   if (!chained_queries_ok(q, n, ests_len, exons, n_exons_total, glen, named.p, own))
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad clean query (a range past its buffer, an empty EST, reserved != 0, no exon, an exon two "
@@ -357,16 +349,8 @@ extern "C" int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, con
                                            "front of or ends behind its sequence)");
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   QueryCall call(ctx, "clean chains");
-  const size_t ws_wave = (ws_dirs + ws_rows + sizeof(DevResult) + 255) & ~(size_t)255;      // as clean_kernel lays it out
-  // the grid: 16 waves per compute unit, fewer where one long end exon has made the workspace of a wave large (266 KB for
-  // 4096 genomic bytes under lev_wave<ALIGN>): the workspaces together stay within WS_BUDGET, at one wave per compute
-  // unit at the least, so that one such query costs the batch some parallelism and not an allocation of a gigabyte
-  size_t waves = 0, cus = 0;
-  TRY_HIP(chained_waves(n, waves, cus));
-  if (waves * ws_wave > WS_BUDGET) {
-    const size_t fit = WS_BUDGET / ws_wave > cus ? WS_BUDGET / ws_wave : cus;
-    if (waves > fit) waves = fit;
-  }
+  size_t waves = 0, ws_wave = 0;
+  TRY_HIP(pgpu_clean_grid(n, ws_dirs, ws_rows, waves, ws_wave));
   const ChainedLayout L = chained_layout(ests_len, n_exons_total, n, sizeof *q, sizeof *out, 256, waves * ws_wave);
   TRY_HIP(hipMalloc((void**)&call.d, L.total));
   uint32_t* const d_undersized = (uint32_t*)(call.d + L.extra);      // the flag of a workspace sized too small, in the extra slot
@@ -374,10 +358,10 @@ extern "C" int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, con
   TRY_HIP(chained_upload(call, L, ests, exons, q));
   TRY_HIP(hipMemsetAsync(d_undersized, 0, sizeof(uint32_t), call.st));
   TRY_HIP(call.record(0));
-  hipLaunchKernelGGL(clean_kernel, dim3((unsigned)waves), dim3(64), 0, call.st, pgpu_index_genomic(idx), (uint32_t)glen, call.d,
-                     (const pgpu_factor*)(call.d + L.exons), (const pgpu_clean_query*)(call.d + L.queries), (uint32_t)n,
-                     call.d + L.ws, ws_dirs, ws_rows, (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes,
-                     (pgpu_clean_result*)(call.d + L.results), d_undersized);
+  pgpu_clean_launch(pgpu_index_genomic(idx), (uint32_t)glen, call.d, (const pgpu_factor*)(call.d + L.exons),
+                    (const pgpu_clean_query*)(call.d + L.queries), (uint32_t)n, call.d + L.ws, ws_dirs, ws_rows, waves,
+                    (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes, (pgpu_clean_result*)(call.d + L.results),
+                    d_undersized, call.st);
   TRY_HIP(call.record(1));
   TRY_HIP(chained_download(call, L, out_exons, out_marks, out));
   uint32_t undersized = 0;

@@ -6,12 +6,19 @@
 
 #include "../../include/pintron_gpu.h"
 
+// (the factorization driver of pgpu_fact.hip asks the same of a query it builds on the device)
+#ifdef __HIPCC__
+#define PGPU_GAPS_HD __host__ __device__
+#else
+#define PGPU_GAPS_HD
+#endif
+
 // An EST of at least one byte; every adjacent pair in order on both strings (exon[i].EST_end < exon[i + 1].EST_start,
 // exon[i].GEN_end < exon[i + 1].GEN_start), and its EST gap no longer than its genomic gap (the FATAL of
 // src/est-factorizations.c:1485).  With the coordinates inside [-1, length] (factor_ok) both gaps then lie inside their
 // strings: [EST_end + 1, EST_start - 1] within [0, est_len - 1], and the same on the sequence.  The number of exons is
 // no matter here: a query beyond PGPU_GAPS_MAX_EXONS is refused on the device, and its input has to be good all the same.
-static inline bool gaps_query_ok(const pgpu_gaps_query& x, const pgpu_factor* ex) {
+PGPU_GAPS_HD static inline bool gaps_query_ok(const pgpu_gaps_query& x, const pgpu_factor* ex) {
   if (x.est_len == 0) return false;
   for (uint32_t k = 0; k + 1 < x.n_exons; ++k) {
     const pgpu_factor& d = ex[k];

@@ -22,6 +22,7 @@
 #include "pgpu_wave_dp.h"
 #include "pgpu_burset.h"
 #include "pgpu_gaps.h"
+#include "pgpu_stage_launch.h"
 
 namespace {
 
@@ -116,6 +117,11 @@ thread_local double t_gaps_ms = 0.0;
 
 }  // namespace
 
+void pgpu_gaps_launch(const uint8_t* T, const uint8_t* ests, const pgpu_factor* exons, const pgpu_gaps_query* q, uint32_t n,
+                      size_t waves, pgpu_factor* out_exons, uint8_t* out_steps, pgpu_gaps_result* out, hipStream_t st) {
+  hipLaunchKernelGGL(gaps_kernel, dim3((unsigned)waves), dim3(64), 0, st, T, ests, exons, q, n, out_exons, out_steps, out);
+}
+
 extern "C" double pgpu_index_gap_chains_kernel_ms(void) { return t_gaps_ms; }
 
 extern "C" int pgpu_index_gap_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
@@ -140,9 +146,9 @@ extern "C" int pgpu_index_gap_chains(pgpu_ctx* ctx, const pgpu_index* idx, const
   TRY_HIP(call.timing_events(1));
   TRY_HIP(chained_upload(call, L, ests, exons, q));
   TRY_HIP(call.record(0));
-  hipLaunchKernelGGL(gaps_kernel, dim3((unsigned)waves), dim3(64), 0, call.st, pgpu_index_genomic(idx), call.d,
-                     (const pgpu_factor*)(call.d + L.exons), (const pgpu_gaps_query*)(call.d + L.queries), (uint32_t)n,
-                     (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes, (pgpu_gaps_result*)(call.d + L.results));
+  pgpu_gaps_launch(pgpu_index_genomic(idx), call.d, (const pgpu_factor*)(call.d + L.exons), (const pgpu_gaps_query*)(call.d + L.queries),
+                   (uint32_t)n, waves, (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes,
+                   (pgpu_gaps_result*)(call.d + L.results), call.st);
   TRY_HIP(call.record(1));
   TRY_HIP(chained_download(call, L, out_exons, out_steps, out));
   TRY_HIP(pgpu_ctx_wait(ctx));

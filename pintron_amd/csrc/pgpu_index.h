@@ -70,6 +70,25 @@ void pgpu_cand_launch_count(const uint8_t* recs, const unsigned long long* rec_f
 void pgpu_cand_launch_write(const uint8_t* recs, const unsigned long long* rec_first, uint32_t n, const uint8_t* T, uint32_t tlen,
                             const pgpu_cand_params* prm, pgpu_cand_result* res, const unsigned long long* first_exon,
                             pgpu_factor* exons, hipStream_t st);
+// pgpu_fact.hip: the candidates of n ESTs through clean, gaps and refine, all on the device.  The caller fills everything but
+// the two results; `block` holds fact_layout(n, n_exons_total, pgpu_scan_tmp_bytes(n + 1)).total bytes (pgpu_fact.h), where
+// the outcomes (res), the compact exons and their step bytes are found afterwards.  The candidates are either queries
+// (fq) or a plan's pattern offsets and candidate results (pat_off, cand; fq null); cand_exons may be the block's ex_in
+// itself.  ws_alloc is asked once, for the workspace of clean and refine, after the call's one host wait; the drive ends with
+// a second wait, so `total` (exons of the answer) and `undersized` (clean's flag: the call failed) are set on return.
+struct pgpu_fact_job {
+  const uint8_t* T; uint32_t tlen;
+  const uint8_t* ests;
+  const pgpu_fact_query* fq;
+  const unsigned long long* pat_off; const pgpu_cand_result* cand;
+  const pgpu_factor* cand_exons;
+  uint32_t n, n_exons_total;
+  uint8_t* block;
+  void* (*ws_alloc)(void* user, size_t bytes); void* ws_user;
+  hipEvent_t ev[8];            // null without timing: 0-1 the whole drive, 2-3 clean_kernel, 4-5 gaps_kernel, 6-7 chain_kernel
+  unsigned long long total; uint32_t undersized;
+};
+hipError_t pgpu_fact_drive(pgpu_ctx* ctx, pgpu_fact_job& job, const pgpu_fact_params& prm);
 // PGPU_TRACE_ALLOC=1: every page-locked host allocation of the library on stderr (size, address, call site)
 #include <cstdio>
 #include <cstdlib>

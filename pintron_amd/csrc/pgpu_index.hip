@@ -29,6 +29,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "pgpu_index.h"
+#include "pgpu_fact.h"
 
 // The first KTAB (pgpu_index.h) characters of a pattern position select the suffix-array interval of that
 // KTAB-mer from a table (2 x 4^KTAB x 4 B = 512 KB, L2-resident) instead of ~2 x 17 bisection
@@ -876,6 +877,13 @@ struct pgpu_pairing_plan {
   unsigned long long cand_total = 0;
   hipEvent_t cand_ev[2] = {nullptr, nullptr};
   float cand_ms = 0.f;
+  // factorization stage (pgpu_fact.hip) over the candidates of the last run_candidates
+  bool have_fact = false;
+  uint8_t *d_fact = nullptr, *d_fact_ws = nullptr;      // the driver's block; the workspace of clean and refine
+  size_t fact_cap = 0, fact_ws_cap = 0;
+  unsigned long long fact_total = 0;
+  hipEvent_t fact_ev[8] = {nullptr};
+  float fact_ms[4] = {0};
 };
 
 // device buffer for a pairing plan: from the context's pool when the plan holds it
@@ -899,10 +907,12 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_keep); hipFree(p->d_out); hipFree(p->d_tmp);
     hipFree(p->d_meg_scratch); hipFree(p->d_meg_info); hipFree(p->d_meg_bytes); hipFree(p->d_meg_off); hipFree(p->d_meg_out);
     hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
+    hipFree(p->d_fact); hipFree(p->d_fact_ws);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   for (auto& e : p->meg_ev) if (e) hipEventDestroy(e);
   for (auto& e : p->cand_ev) if (e) hipEventDestroy(e);
+  for (auto& e : p->fact_ev) if (e) hipEventDestroy(e);
   delete p;
 }
 
@@ -1005,7 +1015,7 @@ extern "C" int pgpu_pairing_plan_run(pgpu_ctx* ctx, pgpu_pairing_plan* p, const 
   const dim3 pgrid((unsigned)(p->n_pat ? p->n_pat : 1)), pblk(64);
   p->n_cand = p->n_out = 0;
   p->have_pairs = false;
-  p->have_meg = p->have_cand = false;               // the records and candidates of the run before are gone with its pairings
+  p->have_meg = p->have_cand = p->have_fact = false;   // the records and candidates of the run before are gone with its pairings
   if (p->n_pat == 0) return PGPU_OK;
   if (p->resident) {
     pgpu_ctx_pool_set_owner(ctx, 1, p);               // whatever another resident plan left there is gone from here on
@@ -1063,7 +1073,7 @@ extern "C" int pgpu_pairing_plan_run_meg(pgpu_ctx* ctx, pgpu_pairing_plan* p, co
   if (!ctx || !p || !prm || prm->min_factor_len == 0) return PGPU_EINVAL;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   p->meg_total = 0; p->meg_ms = 0.f;
-  p->have_meg = p->have_cand = false;
+  p->have_meg = p->have_cand = p->have_fact = false;
   if (p->n_pat == 0) return PGPU_OK;
   if (!p->have_pairs || p->last_L != prm->min_factor_len)
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_meg needs the pairings of pgpu_pairing_plan_run with the same min_factor_len");
@@ -1126,7 +1136,7 @@ done:
 // the candidate factorization of every record that pgpu_pairing_plan_run_meg left in HBM (pgpu_cand.hip)
 extern "C" int pgpu_pairing_plan_run_candidates(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_cand_params* prm) {
   if (!ctx || !p || !prm) return PGPU_EINVAL;
-  p->cand_total = 0; p->cand_ms = 0.f; p->have_cand = false;
+  p->cand_total = 0; p->cand_ms = 0.f; p->have_cand = p->have_fact = false;
   if (prm->min_factor_len == 0 || prm->min_factor_len > (1u << 24))
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad candidate parameters (min_factor_len 0 or above 2^24)");
   if (p->n_pat == 0) { p->have_cand = true; return PGPU_OK; }
@@ -1189,6 +1199,90 @@ extern "C" int pgpu_pairing_plan_fetch_candidates(pgpu_ctx* ctx, pgpu_pairing_pl
   TRY_HIP(hipMemcpyAsync(out, p->d_cand_res, p->n_pat * sizeof(pgpu_cand_result), hipMemcpyDeviceToHost, st));
   if (p->cand_total) TRY_HIP(hipMemcpyAsync(exons, p->d_cand_exons, (size_t)p->cand_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
   TRY_HIP(pgpu_ctx_wait(ctx));
+done:
+  return rc;
+}
+
+// every candidate of the last run_candidates through clean, gaps and refine, where it lies (pgpu_fact.hip)
+extern "C" int pgpu_pairing_plan_run_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_fact_params* prm) {
+  if (!ctx || !p || !prm) return PGPU_EINVAL;
+  p->fact_total = 0; p->have_fact = false;
+  for (auto& m : p->fact_ms) m = 0.f;
+  if (!fact_params_ok(*prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad factorization parameters (a suffpref length outside [0, 2^24])");
+  if (!p->have_cand)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_factorizations needs the candidates of pgpu_pairing_plan_run_candidates");
+  if (p->n_pat == 0) { p->have_fact = true; return PGPU_OK; }
+  if (p->resident && pgpu_ctx_pool_owner(ctx, 1) != p)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "the candidates of this resident plan were overwritten by the run of another one");
+  if (p->n_pat > 0x7fffffffull || p->cand_total > 0x7fffffffull)          // as the index form: exon indices are 32 bits wide
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 patterns or candidate exons in one plan");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  if (p->resident) { p->d_fact = nullptr; p->d_fact_ws = nullptr; }            // taken anew: the pool may have moved
+  int rc = PGPU_OK;
+  const pgpu_index* ix = p->idx;
+  pgpu_range_push("factorizations");
+  struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
+  const FactLayout L = fact_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
+  pgpu_fact_job job;
+  if (L.total > p->fact_cap || !p->d_fact) {
+    if (!p->pooled) hipFree(p->d_fact);
+    p->d_fact = nullptr;
+    p->fact_cap = L.total + L.total / 8;
+    NEED(p->d_fact = plan_alloc<uint8_t>(p, 27, p->fact_cap));
+  }
+  if (pgpu_ctx_timing(ctx) && !p->fact_ev[0]) for (auto& e : p->fact_ev) TRY_HIP(hipEventCreate(&e));
+  job.T = ix->d_gen; job.tlen = (uint32_t)ix->len; job.ests = p->d_pats;
+  job.fq = nullptr; job.pat_off = p->d_pat_off; job.cand = p->d_cand_res; job.cand_exons = p->d_cand_exons;
+  job.n = (uint32_t)p->n_pat; job.n_exons_total = (uint32_t)p->cand_total;
+  job.block = p->d_fact;
+  job.ws_alloc = [](void* user, size_t bytes) -> void* {
+    pgpu_pairing_plan* q = (pgpu_pairing_plan*)user;
+    if (bytes > q->fact_ws_cap || !q->d_fact_ws) {
+      if (!q->pooled) hipFree(q->d_fact_ws);
+      q->d_fact_ws = plan_alloc<uint8_t>(q, 28, bytes);
+      q->fact_ws_cap = q->d_fact_ws ? bytes : 0;
+    }
+    return q->d_fact_ws;
+  };
+  job.ws_user = p;
+  for (int k = 0; k < 8; ++k) job.ev[k] = p->fact_ev[k];
+  TRY_HIP(pgpu_fact_drive(ctx, job, *prm));
+  if (job.undersized) {
+    rc = pgpu_ctx_fail(ctx, PGPU_EDEVICE, "factorizations: the workspace of a wave was sized too small for an end-exon alignment");
+    goto done;
+  }
+  p->fact_total = job.total;
+  if (p->fact_ev[0]) for (int k = 0; k < 4; ++k) hipEventElapsedTime(&p->fact_ms[k], p->fact_ev[2 * k], p->fact_ev[2 * k + 1]);
+  p->have_fact = true;
+done:
+  return rc;
+}
+
+extern "C" uint64_t pgpu_pairing_plan_factorization_exons(const pgpu_pairing_plan* p) { return p ? p->fact_total : 0; }
+extern "C" double pgpu_pairing_plan_factorizations_ms(const pgpu_pairing_plan* p, int k) {
+  return (p && k >= 0 && k < 4) ? p->fact_ms[k] : 0.0;
+}
+
+extern "C" int pgpu_pairing_plan_fetch_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_fact_result* out, pgpu_factor* exons,
+                                                      uint8_t* steps, size_t cap) {
+  if (!ctx || !p || (p->n_pat && !out) || (cap && (!exons || !steps))) return PGPU_EINVAL;
+  if (!p->have_fact) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_factorizations needs pgpu_pairing_plan_run_factorizations first");
+  if (p->resident && p->n_pat && pgpu_ctx_pool_owner(ctx, 1) != p)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "the results of this resident plan were overwritten by the run of another one");
+  if (cap < p->fact_total) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  int rc = PGPU_OK;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_pat == 0) return PGPU_OK;
+  {
+    const FactLayout L = fact_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
+    TRY_HIP(hipMemcpyAsync(out, p->d_fact + L.res, p->n_pat * sizeof(pgpu_fact_result), hipMemcpyDeviceToHost, st));
+    if (p->fact_total) {
+      TRY_HIP(hipMemcpyAsync(exons, p->d_fact + L.out_exons, (size_t)p->fact_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
+      TRY_HIP(hipMemcpyAsync(steps, p->d_fact + L.out_steps, (size_t)p->fact_total, hipMemcpyDeviceToHost, st));
+    }
+    TRY_HIP(pgpu_ctx_wait(ctx));
+  }
 done:
   return rc;
 }

@@ -1012,70 +1012,13 @@ unsigned ef_chain_candidate(const void* rec, const ef_config* cfg, const char* G
   return 3;
 }
 
-ef_est* ef_get_est_factorizations(const ef_seq* est_info, ef_meg* V, const ef_config* cfg,
-                                  const ef_seq* gen_info, ef_backend* be) {
-  ef_phase(EFP_EMBED);
-  ef_est* est = (ef_est*)calloc(1, sizeof(ef_est));
-  est->info = est_info;
+/* What get_EST_factorizations does to the cleaned candidates of one EST before correct_tail: FILTER 1, FILTER 3, FILTER 4
+ * (check_gap_errors), max_number_of_factorizations and the intron refinement loop with its first-exon rule (:278-490).
+ * Returns the list (it may be a new one).  Shared by ef_get_est_factorizations and ef_chain_factorization. */
+static ef_list* filter_and_refine(ef_list* flist, unsigned est_len, const ef_seq* est_info, const ef_seq* gen_info,
+                                  const ef_config* cfg, ef_backend* be) {
   const char* GEN = gen_info->seq;
   const char* EST = est_info->seq;
-  const unsigned est_len = (unsigned)V->n - 2;
-  ef_list* flist = efl_new();
-  ef_work wk = { 0, work_limit(cfg) };
-  emb* chain = NULL;
-  if (V->rec && !V->v && ef_chain_fast_path && chain_embedding(V->rec, cfg, GEN, &wk, &chain)) {
-    if (ef_prof_on) ++ef_prof.chain_graphs;
-    if (wk.used > wk.limit) {                          /* budget spent (:190-193): the caller retries */
-      if (chain) embedding_free(chain);
-      efl_free(flist, ef_factorization_free);
-      free(est);
-      return NULL;
-    }
-    if (chain) {
-      ef_list* embs = efl_new();
-      efl_push_back(embs, chain);
-      ef_list* cands = factorizations_from_embeddings(embs, cfg);
-      efl_free(embs, embedding_free);
-      flist = clean_candidates(cands, flist, est_len, GEN, EST, cfg, be);
-    }
-  } else {
-  if (ef_prof_on) ++ef_prof.other_graphs;
-  V = ef_meg_lists(V);                                 /* a graph known by its record only gets its lists now */
-  EF_MEG_FOR_POS(V, i, 0, V->n) {
-    ef_iter it = efl_begin(V->v[i]);
-    while (efi_has_next(&it)) { ef_pairing* p = (ef_pairing*)efi_next(&it); p->visited = false; p->emb_memo = NULL; }
-  }
-  EF_MEG_FOR_POS(V, i, 0, V->n) {
-    ef_iter it = efl_begin(V->v[i]);
-    while (efi_has_next(&it)) {
-      ef_pairing* root = (ef_pairing*)efi_next(&it);
-      if (root->visited) continue;
-      ef_phase(EFP_EMBED);
-      ef_list* embs = subtree_embeddings(root, cfg, GEN, &wk);
-      if (!embs) {
-        /* budget spent (:190-193): nothing of this attempt is kept, the caller retries */
-        EF_MEG_FOR_POS(V, j, 0, V->n) {
-          ef_iter jt = efl_begin(V->v[j]);
-          while (efi_has_next(&jt)) { ef_pairing* q = (ef_pairing*)efi_next(&jt); if (q->emb_memo) { efl_free(q->emb_memo, embedding_free); q->emb_memo = NULL; } }
-        }
-        efl_free(flist, ef_factorization_free);
-        free(est);
-        return NULL;
-      }
-      flist = clean_candidates(factorizations_from_embeddings(embs, cfg), flist, est_len, GEN, EST, cfg, be);
-    }
-  }
-  /* release the memoised embeddings */
-  EF_MEG_FOR_POS(V, i, 0, V->n) {
-    ef_iter it = efl_begin(V->v[i]);
-    while (efi_has_next(&it)) { ef_pairing* p = (ef_pairing*)efi_next(&it); if (p->emb_memo) { efl_free(p->emb_memo, embedding_free); p->emb_memo = NULL; } }
-  }
-  }
-  {
-    unsigned long long hw = __atomic_load_n(&work_high_water, __ATOMIC_RELAXED);
-    while (wk.used > hw && !__atomic_compare_exchange_n(&work_high_water, &hw, wk.used, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { }
-  }
-
   ef_phase(EFP_FILTERS);
   /* FILTER 1: coverage (:278-331) */
   {
@@ -1212,6 +1155,113 @@ ef_est* ef_get_est_factorizations(const ef_seq* est_info, ef_meg* V, const ef_co
     for (size_t k = 0; k < n_pre; ++k) { ef_gap_window_release(&pre[k].w); ef_dp_res_release(&pre[k].res); }
     free(pre);
   }
+  return flist;
+}
+
+/* One MEG record and one EST through everything ef_get_est_factorizations does for a graph that is one path, up to, not
+ * including, correct_tail: chain_embedding, factorizations_from_embeddings, the cleaning steps, the filters and the
+ * refinement loop -- what pgpu_pairing_plan_run_factorizations computes on the device (include/pintron_gpu.h).  Returns
+ * 0 when the record is flagged or its graph is not one path, 1 when there is no factorization, 2 with the exons in
+ * out_exons (at most cap are written; *n_exons is the number there are).  The work budget and
+ * max_number_of_factorizations < 0 stay with the caller.  est-fact does not call this. */
+unsigned ef_chain_factorization(const void* rec, const ef_config* cfg, const char* EST, const char* GEN, ef_backend* be,
+                                ef_factor* out_exons, size_t cap, unsigned* n_exons) {
+  *n_exons = 0;
+  if (((const uint32_t*)rec)[2] & 3u) return 0;
+  ef_work wk = { 0, ~0ull };
+  emb* chain = NULL;
+  if (!chain_embedding(rec, cfg, GEN, &wk, &chain)) return 0;
+  if (!chain) return 1;
+  ef_seq est_info, gen_info;
+  memset(&est_info, 0, sizeof est_info); memset(&gen_info, 0, sizeof gen_info);
+  est_info.seq = est_info.original_seq = (char*)EST;
+  gen_info.seq = gen_info.original_seq = (char*)GEN;
+  const unsigned est_len = (unsigned)strlen(EST);
+  ef_list* embs = efl_new();
+  efl_push_back(embs, chain);
+  ef_list* cands = factorizations_from_embeddings(embs, cfg);
+  efl_free(embs, embedding_free);
+  ef_list* flist = clean_candidates(cands, efl_new(), est_len, GEN, EST, cfg, be);
+  flist = filter_and_refine(flist, est_len, &est_info, &gen_info, cfg, be);
+  unsigned outcome = 1;
+  if (!efl_empty(flist)) {
+    outcome = 2;
+    ef_iter it = efl_begin((ef_list*)efl_head(flist));
+    while (efi_has_next(&it)) {
+      const ef_factor* x = (const ef_factor*)efi_next(&it);
+      if (*n_exons < cap) out_exons[*n_exons] = *x;
+      ++*n_exons;
+    }
+  }
+  efl_free(flist, ef_factorization_free);
+  return outcome;
+}
+
+ef_est* ef_get_est_factorizations(const ef_seq* est_info, ef_meg* V, const ef_config* cfg,
+                                  const ef_seq* gen_info, ef_backend* be) {
+  ef_phase(EFP_EMBED);
+  ef_est* est = (ef_est*)calloc(1, sizeof(ef_est));
+  est->info = est_info;
+  const char* GEN = gen_info->seq;
+  const char* EST = est_info->seq;
+  const unsigned est_len = (unsigned)V->n - 2;
+  ef_list* flist = efl_new();
+  ef_work wk = { 0, work_limit(cfg) };
+  emb* chain = NULL;
+  if (V->rec && !V->v && ef_chain_fast_path && chain_embedding(V->rec, cfg, GEN, &wk, &chain)) {
+    if (ef_prof_on) ++ef_prof.chain_graphs;
+    if (wk.used > wk.limit) {                          /* budget spent (:190-193): the caller retries */
+      if (chain) embedding_free(chain);
+      efl_free(flist, ef_factorization_free);
+      free(est);
+      return NULL;
+    }
+    if (chain) {
+      ef_list* embs = efl_new();
+      efl_push_back(embs, chain);
+      ef_list* cands = factorizations_from_embeddings(embs, cfg);
+      efl_free(embs, embedding_free);
+      flist = clean_candidates(cands, flist, est_len, GEN, EST, cfg, be);
+    }
+  } else {
+  if (ef_prof_on) ++ef_prof.other_graphs;
+  V = ef_meg_lists(V);                                 /* a graph known by its record only gets its lists now */
+  EF_MEG_FOR_POS(V, i, 0, V->n) {
+    ef_iter it = efl_begin(V->v[i]);
+    while (efi_has_next(&it)) { ef_pairing* p = (ef_pairing*)efi_next(&it); p->visited = false; p->emb_memo = NULL; }
+  }
+  EF_MEG_FOR_POS(V, i, 0, V->n) {
+    ef_iter it = efl_begin(V->v[i]);
+    while (efi_has_next(&it)) {
+      ef_pairing* root = (ef_pairing*)efi_next(&it);
+      if (root->visited) continue;
+      ef_phase(EFP_EMBED);
+      ef_list* embs = subtree_embeddings(root, cfg, GEN, &wk);
+      if (!embs) {
+        /* budget spent (:190-193): nothing of this attempt is kept, the caller retries */
+        EF_MEG_FOR_POS(V, j, 0, V->n) {
+          ef_iter jt = efl_begin(V->v[j]);
+          while (efi_has_next(&jt)) { ef_pairing* q = (ef_pairing*)efi_next(&jt); if (q->emb_memo) { efl_free(q->emb_memo, embedding_free); q->emb_memo = NULL; } }
+        }
+        efl_free(flist, ef_factorization_free);
+        free(est);
+        return NULL;
+      }
+      flist = clean_candidates(factorizations_from_embeddings(embs, cfg), flist, est_len, GEN, EST, cfg, be);
+    }
+  }
+  /* release the memoised embeddings */
+  EF_MEG_FOR_POS(V, i, 0, V->n) {
+    ef_iter it = efl_begin(V->v[i]);
+    while (efi_has_next(&it)) { ef_pairing* p = (ef_pairing*)efi_next(&it); if (p->emb_memo) { efl_free(p->emb_memo, embedding_free); p->emb_memo = NULL; } }
+  }
+  }
+  {
+    unsigned long long hw = __atomic_load_n(&work_high_water, __ATOMIC_RELAXED);
+    while (wk.used > hw && !__atomic_compare_exchange_n(&work_high_water, &hw, wk.used, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { }
+  }
+
+  flist = filter_and_refine(flist, est_len, est_info, gen_info, cfg, be);
   ef_phase(EFP_TAIL);
   /* tail correction and polyA (:573-585) -- on the ORIGINAL EST sequence */
   est->polyA_signals = efl_new();

@@ -415,6 +415,11 @@ typedef struct { int EST_start, EST_end, GEN_start, GEN_end; } ef_factor;   /* 0
  * 3 one candidate with its exons, the embedding's length and the work units charged (ef_fact.c) */
 unsigned ef_chain_candidate(const void* rec, const ef_config* cfg, const char* GEN, ef_factor* out_exons, size_t cap,
                             unsigned* n_exons, unsigned* n_pairs, unsigned* work);
+/* one MEG record and one EST (working sequences, NUL-terminated) through everything ef_get_est_factorizations does for a
+ * graph that is one path, up to, not including, correct_tail: 0 not one path (or flagged), 1 no factorization, 2 the exons
+ * (ef_fact.c).  What pgpu_pairing_plan_run_factorizations answers on the device; est-fact does not call it */
+unsigned ef_chain_factorization(const void* rec, const ef_config* cfg, const char* EST, const char* GEN, struct ef_backend* be,
+                                ef_factor* out_exons, size_t cap, unsigned* n_exons);
 /* a factorization = ef_list of ef_factor*; a list of factorizations = ef_list of ef_list* */
 
 typedef struct {
