@@ -434,6 +434,106 @@ int pgpu_index_gap_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_gap_chains_kernel_ms(void);
 
+/* What est-fact does to a factorization directly behind the refinement loop, chained: the end of get_EST_factorizations
+ * (correct_composition_tail and detect_polyA_signal, src/detect-polya.c:42-166, called at src/est-factorizations.c:573-585)
+ * and the first steps of refine_EST_factorizations that concern one factorization alone (src/factorization-refinement.c:
+ * remove_invalid_factorizations :120-165, recover_lost_prefixes_and_suffixes :1177-1266, remove_false_small_exons
+ * :959-1125).  One query = one factorization; the call is synchronous and batched like pgpu_index_gap_chains, and its exon
+ * arrays have the same shape.  remove_duplicated_factorizations compares factorizations with each other and stays with the
+ * caller.  Nothing in the library calls this entry yet. */
+#define PGPU_TAIL_MAX_EXONS         64   /* exons of one factorization; beyond: PGPU_ERANGE for that query */
+#define PGPU_TAIL_MAX_AFFIX        256   /* EST bytes of a lost prefix / suffix window whose DP has to run; beyond: same */
+#define PGPU_TAIL_MAX_SMALL_WINDOW 128   /* EST bytes of the BORDERS pattern of a small-exon analysis; beyond: same */
+#define PGPU_TAIL_MAX_SMALL_GEN    256   /* genomic bytes of an analysed exon whose edit distance has to run; beyond: same */
+#define PGPU_TAIL_UB_MED_EXON      100   /* _UB_MED_EXON_: a longer exon (on the EST) is not analysed in step 5 */
+#define PGPU_TAIL_AFFIXES_LENGTH     5   /* _AFFIXES_LENGTH_: what step 5 takes of the two neighbours */
+typedef struct {
+  uint64_t est_off; uint32_t est_len;   /* the WORKING sequence (polyA/T masked) = ests + est_off, est_len bytes, 1 .. 2^31 - 1:
+                                           steps 4 and 5 */
+  uint32_t first_exon, n_exons;         /* the factorization = exons[first_exon .. first_exon + n_exons) */
+  uint32_t reserved;                    /* 0 */
+  uint64_t orig_off;                    /* the ORIGINAL sequence = ests + orig_off, est_len bytes too: steps 1 and 2; may
+                                           equal est_off */
+} pgpu_tail_query;                      /* 32 bytes: 0, 8, 12, 16, 20, 24; no padding */
+typedef struct {
+  int32_t  status;       /* PGPU_OK or PGPU_ERANGE */
+  uint8_t  verdict;      /* 0 kept; 1 removed by remove_invalid_factorizations */
+  uint8_t  polyA;        /* detect_polyA_signal's return value */
+  uint8_t  polyadenil;   /* its *polyadenil */
+  uint8_t  recovered;    /* bit 0: a prefix was recovered, bit 1: a suffix */
+  uint32_t n_kept;       /* exons left after step 5 (verdict 0); 0 otherwise */
+  uint32_t tail_added;   /* bases step 1 added to the last exon */
+} pgpu_tail_result;      /* 16 bytes */
+
+/* The five steps, in the program's order.  `orig` and `est` are the two sequences of the query, el = est_len; G is the
+ * resident sequence, gl its length; every comparison of bytes is plain equality (N is no wildcard, case matters) unless a
+ * step says otherwise; "a or A" is the test of the reference's loops.
+ *  - Step 1, correct_composition_tail, on orig: with `tail` the last exon, i = tail.EST_end + 1 and j = tail.GEN_end + 1
+ *    advance together while i < el, j < gl and orig[i] == G[j]; then tail.EST_end = i - 1, tail.GEN_end = j - 1 and
+ *    tail_added is the number of steps.  It runs before the validity test, on whatever the last exon holds.
+ *  - Step 2, detect_polyA_signal, on orig and the tail as step 1 left it, the loops as written: with cl = orig + tail.EST_end
+ *    + 1 of cll = el - tail.EST_end - 1 bytes, i = matches = 0; while i < cll and not stop: on a or A, stop when matches >= 8,
+ *    else count it and go on; on anything else, stop when matches >= 8, else i = cll.  So `stop` needs eight leading a / A
+ *    and a ninth byte of any kind.  Only with stop: (a) polyadenil: for i in [max(0, GEN_end - 39), GEN_end], where G[i] is a
+ *    or A, the six bytes from i -- fewer where the sequence ends, and then no match -- equal aataaa, AATAAA, attaaa or ATTAAA.
+ *    (b) i = max(0, GEN_end - 9), matches = 0; while i <= GEN_end + 10, stop and i < gl: if matches >= 6, stop = false;
+ *    otherwise a or A counts and anything else sets matches to 0, and i advances.  (c) with stop still: i = GEN_end + 1, count
+ *    = 0; while i <= GEN_end + 10, stop and i < gl: if count >= 7, stop = false; otherwise a or A counts, and i advances.  Each
+ *    of (b) and (c) tests its counter before it reads: a counter that fills on the last byte the loop may read cancels
+ *    nothing.  polyA = stop.  Both flags are reported whatever step 3 says.
+ *  - Step 3, remove_invalid_factorizations: verdict 1 when some exon has EST_start > EST_end or GEN_start > GEN_end, or some
+ *    adjacent pair has exon[i].EST_end >= exon[i + 1].EST_start or exon[i].GEN_end >= exon[i + 1].GEN_start.  On verdict 1
+ *    out_exons is what step 1 left, the steps are 0, n_kept and recovered are 0; tail_added and the flags stay.
+ *  - Step 4, recover_lost_prefixes_and_suffixes, on est.  Both windows are taken from the exons as step 1 left them, then
+ *    both answers are applied.  Prefix, with f the first exon, only when f.EST_start > 0 and f.GEN_start > 0: flen = min(
+ *    f.EST_start, f.GEN_start), cap = (int)((1.0 + 0.17) * flen) in double arithmetic, elen = min(f.EST_start, cap), glen =
+ *    min(f.GEN_start, cap); the windows are read BACKWARDS from the exon: e[i] = est[f.EST_start - 1 - i], g[i] = G[f.GEN_start
+ *    - 1 - i].  When e[0] == g[0] nothing is asked.  Otherwise find_longest_affix(e, elen, g, glen) -- PGPU_DP_AFFIX's answer,
+ *    bit for bit, a tie in weight going to the cell scanned later -- and when it is valid f.EST_start -= its EST cut,
+ *    f.GEN_start -= its genomic cut.  Suffix, with l the last exon, only when el - l.EST_end > 1 and gl - l.GEN_end > 1: flen =
+ *    min(el - l.EST_end - 1, gl - l.GEN_end - 1) and both windows have flen bytes (the reference's `(int)(1.0 + rate) * flen`
+ *    is 1 * flen), starting ON the exon's last byte: est + l.EST_end, G + l.GEN_end.  Equal first bytes: nothing is asked.
+ *    Otherwise the same DP, forwards, and when valid l.EST_end += its EST cut, l.GEN_end += its genomic cut.
+ *  - Step 5, remove_false_small_exons / analyze_possibly_small_exon, on est: the exons are walked with prev / curr / next.  An
+ *    exon without a prev or a next, or of more than PGPU_TAIL_UB_MED_EXON EST bytes, is not analysed.  Otherwise, with A =
+ *    PGPU_TAIL_AFFIXES_LENGTH: estart = max(prev.EST_start + 1, prev.EST_end + 1 - A), eend = min(next.EST_end, next.EST_start
+ *    + A), epreflen = prev.EST_end + 1 - estart, esufflen = eend - next.EST_start, allelen = eend - estart, and gstart, gend,
+ *    gpreflen, gsufflen, allglen the same on G.  Three edit distances (compute_edit_distance: PGPU_DP_ED's answer, and 0
+ *    without a DP when the two strings are equal): the exon against its genomic bytes; est[estart, +epreflen) against
+ *    G[gstart, +gpreflen); and the "suffix" pair the reference takes IN FRONT of the window start, est[estart - esufflen,
+ *    +esufflen) against G[gstart - gsufflen, +gsufflen), which is 0 unless estart >= esufflen and gstart >= gsufflen (the
+ *    reference reads in front of its strings there).  Then general_refine_borders(est + estart, allelen, G + gstart, allglen)
+ *    with p0 = 0, p1 = allelen, max_errs = the three distances summed and tail = min(2, gl - gend): PGPU_DP_BORDERS's answer.
+ *    The genomic window spans two introns and has no cap: only its first and last min(allelen + max_errs, allglen) bytes are
+ *    read.  Refused (ok == 0): outcome 1.  Otherwise new = getBursetFrequency_adaptor(G, gstart + off_t1, gstart + off_t2)
+ *    and old = the adaptor's values at (prev.GEN_end + 1, curr.GEN_start) and at (curr.GEN_end + 1, next.GEN_start), summed;
+ *    2 * new < old: outcome 2, nothing changes.  Else (equality included) outcome 3: prev.EST_end = estart + off_p - 1,
+ *    next.EST_start = eend + off_p - allelen, prev.GEN_end = gstart + off_t1 - 1, next.GEN_start = gend + off_t2 - allglen,
+ *    curr is removed, and the merged prev is analysed again as curr, with the exon before it as prev (none at the head) and
+ *    the same next.  After any other outcome the walk moves on by one exon.  The reference asserts off_t1 <= off_t2; here a
+ *    merge with off_t1 > off_t2 is made as the host code makes it, and a later analysis that finds prev.GEN_end >=
+ *    curr.GEN_start or curr.GEN_end >= next.GEN_start (where the reference's unsigned lengths would wrap) is outcome 1.
+ *  - out_exons (n_exons_total entries) and out_steps (n_exons_total bytes) are parallel to exons; exons no query names are
+ *    copied, with step 0.  out_steps[i]: bits 0-1 the outcome of the last analysis of that exon in step 5 (0 not analysed,
+ *    1 refinement refused, 2 accepted but the Burset frequency fell, 3 removed); bit 4: a prefix was recovered into this
+ *    exon; bit 5: a suffix; bit 6: step 1 moved its end.  A removed exon's out_exons entry holds it as it was when removed.
+ *    n_kept = n_exons less the removed ones.
+ *  - Caps refuse only the query that meets them, and only when the DP they bound would run: more than PGPU_TAIL_MAX_EXONS
+ *    exons; an affix window of more than PGPU_TAIL_MAX_AFFIX EST bytes whose first bytes differ; an analysis whose allelen
+ *    exceeds PGPU_TAIL_MAX_SMALL_WINDOW; an analysed exon of more than PGPU_TAIL_MAX_SMALL_GEN genomic bytes (its strings
+ *    cannot be equal, so its edit distance would run).  The result is PGPU_ERANGE with every other field 0, the exons are
+ *    copied as they came in and their steps are 0, whichever step met the cap.
+ *  - PGPU_EINVAL for the whole call: what pgpu_index_gap_chains lists for the fields the two query structs share (with
+ *    est_len == 0), orig_off + est_len > ests_len, and any exon coordinate outside [0, est_len) on the EST or [0, gl) on the
+ *    sequence.  Order between the exons is no rule of the input: it is step 3's verdict.
+ *  - n == 0 is PGPU_OK (out_exons = exons, out_steps = 0).  idx may be built or loaded. */
+int pgpu_index_tail_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                           const pgpu_factor* exons, size_t n_exons_total, const pgpu_tail_query* q, size_t n,
+                           pgpu_factor* out_exons, uint8_t* out_steps, pgpu_tail_result* out);
+/* HIP-event time of the kernel of the calling thread's last pgpu_index_tail_chains on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_tail_chains_kernel_ms(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */

@@ -102,6 +102,16 @@ class GapsResult(C.Structure):     # pgpu_gaps_result
     _fields_ = [("status", C.c_int32), ("verdict", C.c_uint32), ("total_edit", C.c_uint32), ("n_kept", C.c_uint32)]
 
 
+class TailQuery(C.Structure):      # pgpu_tail_query
+    _fields_ = [("est_off", C.c_uint64), ("est_len", C.c_uint32), ("first_exon", C.c_uint32), ("n_exons", C.c_uint32),
+                ("reserved", C.c_uint32), ("orig_off", C.c_uint64)]
+
+
+class TailResult(C.Structure):     # pgpu_tail_result
+    _fields_ = [("status", C.c_int32), ("verdict", C.c_uint8), ("polyA", C.c_uint8), ("polyadenil", C.c_uint8),
+                ("recovered", C.c_uint8), ("n_kept", C.c_uint32), ("tail_added", C.c_uint32)]
+
+
 class CandParams(C.Structure):     # pgpu_cand_params
     _fields_ = [("min_factor_len", C.c_uint32), ("min_intron_length", C.c_int32)]
 
@@ -146,6 +156,11 @@ CLEAN_RESULT_DTYPE = [("status", "<i4"), ("verdict", "<u4"), ("first_kept", "<u4
 GAPS_MAX_EXONS, GAPS_MAX_EST_GAP, GAPS_MAX_ERRORS = 64, 64, 20
 GAPS_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u4"), ("reserved", "<u4")]
 GAPS_RESULT_DTYPE = [("status", "<i4"), ("verdict", "<u4"), ("total_edit", "<u4"), ("n_kept", "<u4")]
+TAIL_MAX_EXONS, TAIL_MAX_AFFIX, TAIL_MAX_SMALL_WINDOW, TAIL_MAX_SMALL_GEN = 64, 256, 128, 256
+TAIL_UB_MED_EXON, TAIL_AFFIXES_LENGTH = 100, 5
+TAIL_QUERY_DTYPE = GAPS_QUERY_DTYPE + [("orig_off", "<u8")]
+TAIL_RESULT_DTYPE = [("status", "<i4"), ("verdict", "u1"), ("polyA", "u1"), ("polyadenil", "u1"), ("recovered", "u1"),
+                     ("n_kept", "<u4"), ("tail_added", "<u4")]
 CAND_NONE, CAND_NOT_PATH, CAND_REFUSED, CAND_ONE = range(4)
 MEG_TOO_COMPLEX, MEG_UNAVAILABLE = 1, 2
 CAND_PARAMS_DTYPE = [("min_factor_len", "<u4"), ("min_intron_length", "<i4")]
@@ -169,6 +184,7 @@ assert C.sizeof(Factor) == 16 and C.sizeof(RefineQuery) == 96 and C.sizeof(Refin
 assert C.sizeof(ChainQuery) == 40 and C.sizeof(ChainResult) == 16
 assert C.sizeof(CleanQuery) == 32 and C.sizeof(CleanResult) == 16
 assert C.sizeof(GapsQuery) == 24 and C.sizeof(GapsResult) == 16
+assert C.sizeof(TailQuery) == 32 and C.sizeof(TailResult) == 16
 assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
 assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
 
@@ -182,6 +198,7 @@ EXPORTS = [
     "pgpu_index_refine_chains", "pgpu_index_refine_chains_kernel_ms",
     "pgpu_index_clean_chains", "pgpu_index_clean_chains_kernel_ms",
     "pgpu_index_gap_chains", "pgpu_index_gap_chains_kernel_ms",
+    "pgpu_index_tail_chains", "pgpu_index_tail_chains_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -258,6 +275,10 @@ def lib():
                                             C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(GapsResult)]
         L.pgpu_index_gap_chains_kernel_ms.argtypes = []
         L.pgpu_index_gap_chains_kernel_ms.restype = C.c_double
+        L.pgpu_index_tail_chains.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(TailQuery), sz,
+                                             C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(TailResult)]
+        L.pgpu_index_tail_chains_kernel_ms.argtypes = []
+        L.pgpu_index_tail_chains_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -552,6 +573,23 @@ class Index:
 
     def gap_chains_kernel_ms(self):
         return self.ctx.L.pgpu_index_gap_chains_kernel_ms()
+
+    def tail_chains_raw(self, ests: bytes, exons, queries, n: int):
+        """One pgpu_index_tail_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+        TAIL_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of TAIL_RESULT_DTYPE)."""
+        return self._chained_raw(self.ctx.L.pgpu_index_tail_chains, TailQuery, TailResult, TAIL_RESULT_DTYPE,
+                                 ests, exons, queries, n)
+
+    def tail_chains(self, ests: bytes, exons, queries):
+        """What est-fact does to every factorization `queries` names directly behind the refinement loop (tail correction,
+        polyA, validity, lost prefix and suffix, false small exons, chained on the device): (out_exons, out_steps,
+        results) as numpy arrays."""
+        rc, out_exons, out_steps, res = self.tail_chains_raw(ests, exons, queries, len(queries))
+        self.ctx.check(rc)
+        return out_exons, out_steps, res
+
+    def tail_chains_kernel_ms(self):
+        return self.ctx.L.pgpu_index_tail_chains_kernel_ms()
 
     def candidates_raw(self, records: bytes, rec_first, n: int, min_factor_len, min_intron_length, exons_cap: int):
         """One pgpu_index_candidates call as it is: `records` the concatenated MEG records, `rec_first` a numpy uint64 array

@@ -1,8 +1,8 @@
-// The host side of a query on the resident index, once: what the seven entries pgpu_index_find, pgpu_index_classify,
-// pgpu_index_small_exons, pgpu_index_refine_introns, pgpu_index_refine_chains, pgpu_index_clean_chains and
-// pgpu_index_gap_chains share around their kernels.  An entry validates, lays out its device block, copies in, launches,
+// The host side of a query on the resident index, once: what the eight entries pgpu_index_find, pgpu_index_classify,
+// pgpu_index_small_exons, pgpu_index_refine_introns, pgpu_index_refine_chains, pgpu_index_clean_chains,
+// pgpu_index_gap_chains and pgpu_index_tail_chains share around their kernels.  An entry validates, lays out its device block, copies in, launches,
 // copies out and waits, as straight-line code; the QueryCall on its stack owns what has to be given back whichever way the
-// entry returns.  The three chained entries (one query = one list of exons, chained on the device) share more: the chained
+// entry returns.  The four chained entries (one query = one list of exons, chained on the device) share more: the chained
 // path at the end.
 //
 // The contract of every entry (tests/test_gpu_query_calls.py): a refused call and an empty one leave the entry's
@@ -88,7 +88,8 @@ struct QueryCall {
     if (e_ != hipSuccess) return call.fail(e_);         \
   } while (0)
 
-// ---- The chained path: pgpu_index_refine_chains, pgpu_index_clean_chains and pgpu_index_gap_chains.  Their query structs
+// ---- The chained path: pgpu_index_refine_chains, pgpu_index_clean_chains, pgpu_index_gap_chains and
+// pgpu_index_tail_chains.  Their query structs
 // begin with est_off, est_len, first_exon, n_exons and reserved; the calls answer with out_exons and one byte per exon,
 // parallel to `exons` (an exon no query names: a copy and byte 0; an empty call: that for every exon, without a device
 // call), and with one result per query.  An entry keeps what the others do differently: its own rules, its workspace and

@@ -1,7 +1,7 @@
-// The three chained stage kernels (clean_kernel, gaps_kernel, chain_kernel) as plain launches over device pointers, for a
-// caller that has the ESTs, the exons and the queries in HBM already: the factorization driver of pgpu_fact.hip.  Each of
-// pgpu_clean.hip, pgpu_gaps.hip and pgpu_chain.hip launches its kernel through the function below from its public entry
-// too, so there is one launch per kernel.  Beside them the one rule of a public entry that the driver has to repeat on
+// The chained stage kernels (clean_kernel, gaps_kernel, chain_kernel, tail_kernel) as plain launches over device pointers,
+// for a caller that has the ESTs, the exons and the queries in HBM already: the factorization driver of pgpu_fact.hip (which
+// does not append the tail stage yet).  Each of pgpu_clean.hip, pgpu_gaps.hip, pgpu_chain.hip and pgpu_tail.hip launches its
+// kernel through the function below from its public entry too, so there is one launch per kernel.  Beside them the one rule of a public entry that the driver has to repeat on
 // the device: what an end exon of a clean query asks of the per-wave workspace (clean_query_need), __host__ __device__ so
 // that the entry's validator and the driver's hand-off kernel run the same code.
 #pragma once
@@ -71,3 +71,6 @@ size_t pgpu_chain_ws_wave(void);
 void pgpu_chain_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, const pgpu_factor* exons, const pgpu_chain_query* q,
                        uint32_t n, uint8_t* ws, size_t waves, pgpu_factor* out_exons, uint8_t* out_steps, pgpu_chain_result* out,
                        hipStream_t st);
+// pgpu_tail.hip: no workspace; tlen is the length of the resident sequence T
+void pgpu_tail_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, const pgpu_factor* exons, const pgpu_tail_query* q,
+                      uint32_t n, size_t waves, pgpu_factor* out_exons, uint8_t* out_steps, pgpu_tail_result* out, hipStream_t st);

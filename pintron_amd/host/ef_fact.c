@@ -1197,6 +1197,46 @@ unsigned ef_chain_factorization(const void* rec, const ef_config* cfg, const cha
   return outcome;
 }
 
+/* One factorization through what est-fact does to it directly behind the refinement loop: correct_tail and detect_polyA
+ * (on ORIG, the original sequence), then the first steps of ef_refine_est_factorizations (ef_factref.c:
+ * ef_refine_first_steps) on EST, the working sequence -- what pgpu_index_tail_chains computes on the device
+ * (include/pintron_gpu.h).  exons: n_exons in; at most n_exons are written back and *n_out is the number left.  Returns
+ * 1 when remove_invalid dropped the factorization (exons then hold it as correct_tail left it, *n_out = n_exons), else 0.
+ * est-fact does not call this. */
+unsigned ef_chain_tail(const char* EST, const char* ORIG, const char* GEN, ef_backend* be, ef_factor* exons, unsigned n_exons,
+                       unsigned* n_out, unsigned* polyA, unsigned* polyadenil) {
+  ef_seq est_info, gen_info;
+  memset(&est_info, 0, sizeof est_info); memset(&gen_info, 0, sizeof gen_info);
+  est_info.seq = (char*)EST; est_info.original_seq = (char*)ORIG;
+  gen_info.seq = gen_info.original_seq = (char*)GEN;
+  ef_list* f = efl_new();
+  for (unsigned k = 0; k < n_exons; ++k) {
+    ef_factor* x = (ef_factor*)malloc(sizeof(ef_factor));
+    *x = exons[k];
+    efl_push_back(f, x);
+  }
+  correct_tail(f, GEN, ORIG);
+  bool pn = false;
+  *polyA = detect_polyA(f, GEN, ORIG, &pn) ? 1u : 0u;
+  *polyadenil = pn ? 1u : 0u;
+  exons[n_exons - 1] = *(const ef_factor*)efl_tail(f);
+  ef_est e;
+  memset(&e, 0, sizeof e);
+  e.info = &est_info;
+  e.factorizations = efl_new();
+  efl_push_back(e.factorizations, f);
+  ef_refine_first_steps(&gen_info, &e, be);
+  unsigned dropped = 1;
+  *n_out = n_exons;
+  if (!efl_empty(e.factorizations)) {
+    dropped = 0; *n_out = 0;
+    ef_iter it = efl_begin((ef_list*)efl_head(e.factorizations));
+    while (efi_has_next(&it)) exons[(*n_out)++] = *(const ef_factor*)efi_next(&it);
+  }
+  efl_free(e.factorizations, ef_factorization_free);
+  return dropped;
+}
+
 ef_est* ef_get_est_factorizations(const ef_seq* est_info, ef_meg* V, const ef_config* cfg,
                                   const ef_seq* gen_info, ef_backend* be) {
   ef_phase(EFP_EMBED);

@@ -224,6 +224,16 @@ static void remove_false_small_exons(const ef_seq* gen, ef_est* e, ef_backend* b
   }
 }
 
+/* The steps of ef_refine_est_factorizations that concern one factorization alone and come first: remove_invalid,
+ * recover_affixes, remove_false_small_exons -- without remove_duplicated_factorizations between them (it compares
+ * factorizations with each other) and without the asking ahead (it changes no answer).  For ef_chain_tail (ef_fact.c);
+ * est-fact does not call this. */
+void ef_refine_first_steps(const ef_seq* gen, ef_est* e, ef_backend* be) {
+  remove_invalid(e->factorizations);
+  recover_affixes(gen, e, be);
+  remove_false_small_exons(gen, e, be);
+}
+
 static int base2(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 static int kmer_code(const char* s) {
   int code = 0;

@@ -420,6 +420,11 @@ unsigned ef_chain_candidate(const void* rec, const ef_config* cfg, const char* G
  * (ef_fact.c).  What pgpu_pairing_plan_run_factorizations answers on the device; est-fact does not call it */
 unsigned ef_chain_factorization(const void* rec, const ef_config* cfg, const char* EST, const char* GEN, struct ef_backend* be,
                                 ef_factor* out_exons, size_t cap, unsigned* n_exons);
+/* one factorization through correct_tail, detect_polyA (on ORIG) and the first steps of ef_refine_est_factorizations (on
+ * EST): 1 when remove_invalid dropped it, else 0 with the exons that are left (ef_fact.c).  What pgpu_index_tail_chains
+ * answers on the device; est-fact does not call it */
+unsigned ef_chain_tail(const char* EST, const char* ORIG, const char* GEN, struct ef_backend* be, ef_factor* exons, unsigned n_exons,
+                       unsigned* n_out, unsigned* polyA, unsigned* polyadenil);
 /* a factorization = ef_list of ef_factor*; a list of factorizations = ef_list of ef_list* */
 
 typedef struct {
@@ -439,6 +444,9 @@ ef_est* ef_get_est_factorizations(const ef_seq* est, ef_meg* V, const ef_config*
                                   const ef_seq* gen, ef_backend* be);
 /* refine_EST_factorizations & co (src/factorization-refinement.c) */
 void ef_refine_est_factorizations(const ef_seq* gen, ef_est* e, const ef_config* cfg, ef_backend* be);
+/* its first steps that concern one factorization alone (remove_invalid, recover_affixes, remove_false_small_exons), for
+ * ef_chain_tail */
+void ef_refine_first_steps(const ef_seq* gen, ef_est* e, ef_backend* be);
 void ef_remove_factorizations_with_very_small_exons(ef_list* facts);
 void ef_remove_duplicated_factorizations(ef_list* facts);
 /* refine_intron (src/refine-intron.c:47-265) */
