@@ -560,7 +560,11 @@ int pgpu_pairings(pgpu_ctx* ctx, const pgpu_index* idx,
 /* The same in three steps for callers that keep the patterns resident (bench, batched host):
  * create uploads the patterns; run launches every kernel with the given parameters (may be
  * repeated with other parameters: the reference re-runs build_vertex_set with a longer
- * min_factor_len when a MEG is too complex, src/compute-est-fact.c:132-144); fetch downloads. */
+ * min_factor_len when a MEG is too complex, src/compute-est-fact.c:132-144); fetch downloads.
+ * The stages of a plan build on each other -- run, run_meg, run_candidates, run_factorizations, below -- and the run
+ * of a stage takes with it what the stages behind it had made.  On a plan with patterns a fetch whose stage's results
+ * are not there (never made, or gone with a later run of an earlier stage) is PGPU_EINVAL with a message, never
+ * stale data. */
 typedef struct pgpu_pairing_plan pgpu_pairing_plan;
 int pgpu_pairing_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const char* patterns,
                              const uint64_t* pat_off, size_t n_pat, pgpu_pairing_plan** plan);

@@ -18,7 +18,7 @@
 // round, and hipMalloc/hipFree (the latter synchronises the device) would dominate.  A context
 // keeps one grow-only set of buffers per plan type; a plan borrows the set when it is free.
 struct BufPool {
-  static constexpr int SLOTS = 29;
+  static constexpr int SLOTS = PLAN_SLOTS;      // pgpu_index.h
   void* ptr[SLOTS] = {nullptr};
   size_t cap[SLOTS] = {0};
   bool busy = false;
@@ -81,6 +81,20 @@ static void* pinned(pgpu_ctx* ctx, int slot, size_t bytes) {
   return ctx->pin[slot];
 }
 
+extern "C" int pgpu_host_alloc(pgpu_ctx* ctx, size_t bytes, void** out) {
+  if (!ctx || !out) return PGPU_EINVAL;
+  *out = nullptr;
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  if (hipHostMalloc(out, bytes ? bytes : 16, hipHostMallocDefault) != hipSuccess) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "out of page-locked host memory");
+  pgpu_trace_alloc("pgpu_host_alloc", *out, bytes);
+  return PGPU_OK;
+}
+extern "C" int pgpu_host_free(pgpu_ctx* ctx, void* q) {
+  if (!ctx) return PGPU_EINVAL;
+  if (q && hipHostFree(q) != hipSuccess) return pgpu_ctx_fail(ctx, PGPU_EDEVICE, "hipHostFree failed");
+  return PGPU_OK;
+}
+
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool) {
   if (ctx->pools[pool].busy) return false;
   ctx->pools[pool].busy = true;
@@ -104,6 +118,7 @@ const void* pgpu_ctx_pool_owner(const pgpu_ctx* ctx, int pool) { return ctx->poo
 // returns a buffer of at least `bytes` from the (acquired) pool, growing it when needed
 void* pgpu_ctx_pool_get(pgpu_ctx* ctx, int pool, int slot, size_t bytes) {
   BufPool& p = ctx->pools[pool];
+  if (slot < 0 || slot >= BufPool::SLOTS) return nullptr;
   if (bytes == 0) bytes = 16;
   if (p.cap[slot] < bytes) {
     if (p.ptr[slot]) (void)hipFree(p.ptr[slot]);
@@ -829,8 +844,7 @@ extern "C" int pgpu_dp_plan_launch(pgpu_ctx* ctx, pgpu_dp_plan* p) {
     const RouteInfo& ri = ROUTES[g.route];
     hipStream_t st = ri.lane >= 0 ? ctx->aux[ri.lane] : ctx->stream;
     if (g.ev0) HIP_TRY(ctx, hipEventRecord(g.ev0, st));
-    pgpu_range_push(ri.name);
-    struct PopAtExit { ~PopAtExit() { pgpu_range_pop(); } } pop_at_exit;
+    const ProfRange range(ri.name);
     if (g.route == RT_BATCH) {
       if (!launch_dp_batch(p->d_jobs, p->batch.desc, p->batch.bc_max_rows, p->d_results, p->d_ws, p->d_strs, st))
         return set_err(ctx, PGPU_EDEVICE, "batch launch: LDS budget exceeded");

@@ -1,4 +1,4 @@
-// Internal view of the genomic index (pgpu_index.hip).
+// Internal view of the genomic index (pgpu_index.hip) and of the context, for the library's other files.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -13,6 +13,21 @@ size_t pgpu_index_length(const pgpu_index* idx);
 // k-mer has klo == khi
 constexpr uint32_t KTAB = 8;
 constexpr uint32_t KTAB_ENTRIES = 1u << (2 * KTAB);
+__device__ __forceinline__ int kmer_base(uint32_t c) {
+  return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
+}
+// 2-bit code of s[0..KTAB), or -1 when a character is not A/C/G/T (`avail` readable characters)
+__device__ __forceinline__ int kmer_code(const uint8_t* __restrict__ s, uint32_t avail) {
+  if (avail < KTAB) return -1;
+  int code = 0;
+#pragma unroll
+  for (uint32_t x = 0; x < KTAB; ++x) {
+    const int b = kmer_base(s[x]);
+    if (b < 0) return -1;
+    code = (code << 2) | b;
+  }
+  return code;
+}
 
 // What the suffix-array form of find_longest_common_factor_dp needs (pgpu_dp_kernels.hip: lcfsa_wave_body):
 //   focc   first occurrence of every upper-case ACGT l-mer, l = 1..8 (table l at offset (4^l - 4) / 3;
@@ -28,6 +43,18 @@ struct LcfIndexView {
 };
 LcfIndexView pgpu_index_lcf_view(const pgpu_index* idx);
 constexpr uint32_t LCF_FOCC_ENTRIES = 87380;      // 4 + 16 + ... + 4^8
+
+// What the pairing kernels need (pgpu_pairing_plan.hip): the sequence T (n bytes), its suffix array and LCP array
+// (n + 1 entries), the k-mer interval table, the alphabet keys of preprocess_text (256 entries; sigma = number of
+// distinct characters), and the sequence at 2 bits per base with its flag bits (pack_sequence).
+struct PairIndexView {
+  const uint8_t* T; uint32_t n; const uint32_t* sa; const uint32_t* lcp; const uint32_t* klo; const uint32_t* khi;
+  const uint8_t* key; uint32_t sigma; const uint32_t* code; const uint32_t* bad;
+};
+PairIndexView pgpu_index_pair_view(const pgpu_index* idx);
+// src[0..n) (device) -> code (2 * ceil(n / 32) words, + 4 of slack the windows may read) and flag words (ceil(n / 32) + 4):
+// 2 bits per base, and one flag bit per base that is not an upper-case A, C, G or T
+hipError_t pack_sequence(const uint8_t* src, size_t n, uint32_t* code, uint32_t* bad, hipStream_t st);
 
 // Tables that are derived from the sequence on first use and then belong to the index (the classification tables
 // of pgpu_classify.hip): whoever needs them takes `mu`, builds when `tables` is still null, and leaves `release`
@@ -45,6 +72,19 @@ int pgpu_ctx_bind(pgpu_ctx* ctx);
 // for the tens of milliseconds per step its kernels run (PGPU_WAIT: the nap in microseconds, as for DP plans)
 hipError_t pgpu_ctx_wait(pgpu_ctx* ctx);
 int pgpu_ctx_fail(pgpu_ctx* ctx, int code, const char* msg);
+// the context's two pools of device buffers (BufPool, pgpu_api.hip): DP plans keep one block in pool 0; the slots of
+// pool 1 are named after what a pairing plan keeps in them, and their number is the size of every pool
+constexpr int PLAN_POOL = 1;
+enum PlanSlot : int {
+  SLOT_PATS, SLOT_PAT_OFF,
+  SLOT_LO, SLOT_HI, SLOT_A, SLOT_THR, SLOT_CNT, SLOT_CNT_A, SLOT_CNT_B, SLOT_CAND_OFF, SLOT_OUT_OFF, SLOT_OUT_FIRST, SLOT_TMP,
+  SLOT_CAND, SLOT_KEEP, SLOT_OUT,
+  SLOT_MEG_SCRATCH, SLOT_MEG_INFO, SLOT_MEG_BYTES, SLOT_MEG_OFF, SLOT_MEG_OUT,
+  SLOT_PCODE, SLOT_PBAD,
+  SLOT_CAND_RES, SLOT_CAND_CNT, SLOT_CAND_FIRST, SLOT_CAND_EXONS,
+  SLOT_FACT, SLOT_FACT_WS,
+  PLAN_SLOTS
+};
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool);
 void pgpu_ctx_pool_release(pgpu_ctx* ctx, int pool);
 void* pgpu_ctx_pool_get(pgpu_ctx* ctx, int pool, int slot, size_t bytes);
@@ -53,6 +93,15 @@ void pgpu_ctx_pool_unshare(pgpu_ctx* ctx, int pool, const void* who);
 void pgpu_ctx_pool_set_owner(pgpu_ctx* ctx, int pool, const void* who);
 const void* pgpu_ctx_pool_owner(const pgpu_ctx* ctx, int pool);
 bool pgpu_ctx_timing(const pgpu_ctx* ctx);
+// what an entry returns for a HIP error
+inline int pgpu_code_of(hipError_t e) { return e == hipErrorOutOfMemory ? PGPU_ENOMEM : PGPU_EDEVICE; }
+// a profiler range (pgpu_range_push / pgpu_range_pop) that ends with its scope
+struct ProfRange {
+  explicit ProfRange(const char* name) { pgpu_range_push(name); }
+  ~ProfRange() { pgpu_range_pop(); }
+  ProfRange(const ProfRange&) = delete;
+  ProfRange& operator=(const ProfRange&) = delete;
+};
 
 // pgpu_meg.hip: hand-written exclusive prefix sums and the per-pattern MEG kernels
 size_t pgpu_scan_tmp_bytes(size_t n);

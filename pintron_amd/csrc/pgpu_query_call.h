@@ -20,9 +20,6 @@
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// what an entry returns for a HIP error
-inline int pgpu_code_of(hipError_t e) { return e == hipErrorOutOfMemory ? PGPU_ENOMEM : PGPU_EDEVICE; }
-
 // a coordinate of a factor: -1 (unset) or an index into, or the length of, what it refers to (on the device too: the
 // factorization driver of pgpu_fact.hip asks it per query)
 __host__ __device__ inline bool coordinate_ok(int32_t v, size_t len) { return v >= -1 && (v < 0 || (size_t)v <= len); }

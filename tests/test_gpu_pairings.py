@@ -219,3 +219,29 @@ def test_resident_plans_share_their_scratch(gpu_ctx):
         for p in plans:
             p.close()
         idx.close()
+
+
+def test_resident_plans_records_go_with_the_pairings(gpu_ctx):
+    """a.run, a.run_meg, b.run on two resident plans: b's run has taken the shared buffers, so a's MEG records are
+    refused as overwritten -- a's own stages are all there, it is the scratch that is gone."""
+    import pintron_amd.capi as capi
+    from pintron_amd import synth
+    w = synth.make("C2", n_est=40, seed=5)
+    idx = capi.Index(gpu_ctx, w.genomic)
+    a = capi.PairingPlan(gpu_ctx, idx, list(w.est_seqs[:25]), resident=True)
+    b = capi.PairingPlan(gpu_ctx, idx, list(w.est_seqs[25:]), resident=True)
+    try:
+        a.run()
+        assert a.run_meg() > 0
+        want = a.fetch_meg()
+        b.run()
+        with pytest.raises(capi.PgpuError) as e:
+            a.fetch_meg()
+        assert e.value.code == capi.PGPU_EINVAL and "overwritten" in str(e.value)
+        a.run()                                                                  # and a serves again once it has run again
+        a.run_meg()
+        assert a.fetch_meg() == want
+    finally:
+        a.close()
+        b.close()
+        idx.close()
