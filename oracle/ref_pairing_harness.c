@@ -32,12 +32,17 @@ typedef struct {
   pconfiguration cfg;
 } ref_index;
 
-void* ref_index_create(const char* genomic) {
+/* stree_preprocess gives slices only to the nodes of string depth >= min_factor_len
+ * (src/aug_suffix_tree.c:247), and build_vertex_set reads the slices of every node it reports: an
+ * index answers queries with a min_factor_len at or above the one it was preprocessed with, and
+ * crashes below it. */
+void* ref_index_create_len(const char* genomic, unsigned min_factor_len) {
   ref_index* ix = (ref_index*)calloc(1, sizeof(ref_index));
   ix->gen = EST_info_create();
   ix->gen->EST_seq = alloc_and_copy(genomic);
   ix->gen->EST_id = alloc_and_copy(">harness");
   ix->cfg = harness_config();
+  ix->cfg->min_factor_len = min_factor_len;
   LST_StringSet* set = lst_stringset_new();
   LST_String* lst = PALLOC(LST_String);
   lst_string_init(lst, ix->gen->EST_seq, sizeof(char), strlen(ix->gen->EST_seq));
@@ -48,6 +53,8 @@ void* ref_index_create(const char* genomic) {
   stree_preprocess(ix->tree, ix->pg, ix->cfg);
   return ix;
 }
+
+void* ref_index_create(const char* genomic) { return ref_index_create_len(genomic, 15); }
 
 /* triples (p,t,l) of every position list, in list order, source and sink excluded.
  * Returns the number of pairings (may exceed cap; only cap are written). */

@@ -61,21 +61,33 @@ class OracleIndex:
         assert n <= len(self.buf) // 3
         return self.buf[:3 * n].reshape(-1, 3).copy()
 
+    def pairings_depths(self, est: bytes, min_factor_len=15, rate=0.2):
+        """(pairings, D): D[i] = the locus depth D_i the threshold of position i was taken from, 0 below min_factor_len"""
+        depth = np.zeros(max(len(est), 1), dtype=np.int32)
+        n = self.L.orc_pairings(self.h, est, len(est), min_factor_len, rate, self.buf.ctypes.data,
+                                len(self.buf) // 3, depth.ctypes.data)
+        assert n <= len(self.buf) // 3
+        return self.buf[:3 * n].reshape(-1, 3).copy(), depth[:len(est)]
+
     def close(self):
         self.L.orc_index_destroy(self.h)
 
 
 class RefIndex:
-    """The reference's own suffix tree + build_vertex_set (oracle/ref_pairing_harness.c)."""
+    """The reference's own suffix tree + build_vertex_set (oracle/ref_pairing_harness.c).  The tree is
+    preprocessed for one min_factor_len and answers queries at or above it; below it the reference's
+    nodes have no slices and its code crashes, so pairings() refuses."""
 
-    def __init__(self, genomic: bytes):
+    def __init__(self, genomic: bytes, min_factor_len=15):
         R = O.ref_static()   # oracle/ref_pairing_harness.c, linked against the core library
-        R.ref_index_create.restype = C.c_void_p
-        R.ref_index_create.argtypes = [C.c_char_p]
+        R.ref_index_create_len.restype = C.c_void_p
+        R.ref_index_create_len.argtypes = [C.c_char_p, C.c_uint]
         R.ref_build_pairings.restype = C.c_long
         R.ref_build_pairings.argtypes = [C.c_void_p, C.c_char_p, C.c_uint, C.c_double, C.c_void_p, C.c_long]
-        self.R = R
-        self.h = self._quiet(lambda: R.ref_index_create(genomic))
+        self.R, self.min_factor_len = R, int(min_factor_len)
+        if self.min_factor_len < 1:
+            raise ValueError("min_factor_len must be at least 1")
+        self.h = self._quiet(lambda: R.ref_index_create_len(genomic, self.min_factor_len))
         self.buf = np.zeros(3 * 400000, dtype=np.int32)
 
     @staticmethod
@@ -91,8 +103,12 @@ class RefIndex:
             os.close(saved)
 
     def pairings(self, est: bytes, min_factor_len=15, rate=0.2):
+        if min_factor_len < self.min_factor_len:
+            raise ValueError("this RefIndex was built for min_factor_len >= %d, asked for %d"
+                             % (self.min_factor_len, min_factor_len))
         n = self._quiet(lambda: self.R.ref_build_pairings(self.h, est, min_factor_len, rate,
                                                           self.buf.ctypes.data, len(self.buf) // 3))
+        assert n <= len(self.buf) // 3
         return self.buf[:3 * n].reshape(-1, 3).copy()
 
 

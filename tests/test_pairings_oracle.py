@@ -17,15 +17,36 @@ needs_ref = pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built")
 @needs_ref
 @pytest.mark.parametrize("seed", [5, 6, 7])
 def test_repeats_match_reference(seed):
-    gen, ests = PL.repeat_workload(seed)
-    oi, ri = PL.OracleIndex(gen), PL.RefIndex(gen)
-    for L, rate in ((15, 0.2), (16, 0.2), (22, 0.2), (15, 0.5), (15, 0.0), (15, 1.0)):
+    """The reference's tree answers a min_factor_len at or above the one it was preprocessed with:
+    one RefIndex per L below 15.  At L = 3 nearly every position pairs with hundreds of occurrences,
+    so the genomic sequence is cut to 2 000 bases and the lists stay inside the harness buffers."""
+    full, ests = PL.repeat_workload(seed)
+    indexes = {}
+    for L, rate in ((15, 0.2), (16, 0.2), (22, 0.2), (15, 0.5), (15, 0.0), (15, 1.0),
+                    (12, 0.2), (8, 0.2), (7, 0.2), (3, 0.5)):
+        gen = full[:2000] if L == 3 else full
+        built = min(L, 15)
+        if (built, len(gen)) not in indexes:
+            indexes[built, len(gen)] = (PL.OracleIndex(gen), PL.RefIndex(gen, built))
+        oi, ri = indexes[built, len(gen)]
+        n = 0
         for e in ests:
             if not e:
                 continue
             a, b = oi.pairings(e, L, rate), ri.pairings(e, L, rate)
             assert np.array_equal(a, b), (seed, L, rate, len(e), a[:5], b[:5])
-    oi.close()
+            n += len(a)
+        assert n > 0, (seed, L, rate)
+    for oi, _ in indexes.values():
+        oi.close()
+
+
+@needs_ref
+def test_ref_index_refuses_a_shorter_min_factor_len():
+    ri = PL.RefIndex(b"ACGTTGCAAGGCTTAACCGGTTACGATCGATTAGC" * 3, 12)
+    assert ri.pairings(b"GGCTTAACCGGTTACG", 12, 0.2).shape[1] == 3
+    with pytest.raises(ValueError):
+        ri.pairings(b"GGCTTAACCGGTTACG", 11, 0.2)
 
 
 @needs_ref
