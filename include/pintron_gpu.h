@@ -534,6 +534,98 @@ int pgpu_index_tail_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* est
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_tail_chains_kernel_ms(void);
 
+/* The last two routines of refine_EST_factorizations (src/factorization-refinement.c:1270-1305) that concern one
+ * factorization alone, chained: search_for_new_small_exons (:875-912, with search_small_exon_at_prefix :500-606 and
+ * search_small_exon :641-871) and clean_factorizations (:914-950).  One query = one factorization, as
+ * pgpu_index_tail_chains leaves it (the exons it removed taken out); the call is synchronous and batched like that entry.
+ * pgpu_index_tail_chains followed by this entry is the whole of refine_EST_factorizations for an EST with one
+ * factorization.  add_if_not_exists compares factorizations with each other and stays with the caller.  Nothing in the
+ * library calls this entry yet. */
+#define PGPU_SMALL_MAX_EXONS          64   /* exons of a query on entry; the list can grow to 2 * n_exons */
+#define PGPU_SMALL_MAX_PREFIX_WINDOW 256   /* rows (EST bytes, allelen) of the prefix search's BORDERS: lev_wave_body<4,
+                                              BORDERS>, four rows per lane; small_kernel has no scratch and no spilled
+                                              vector register with it */
+#define PGPU_SMALL_MAX_KBAND          31   /* as step 5 of pgpu_index_clean_chains: a genomic exon length above 1 033 */
+typedef pgpu_tail_query pgpu_small_query;      /* est_off = the WORKING sequence (steps 1-2), orig_off = the ORIGINAL (step 3) */
+typedef struct { int32_t min_intron_length; uint32_t reserved; } pgpu_small_params;   /* 8 bytes; config->min_intron_length, any value */
+typedef struct {
+  int32_t  status;        /* PGPU_OK or PGPU_ERANGE */
+  uint8_t  refused;       /* with PGPU_ERANGE, which rule: 1 exons, 2 prefix window, 3 prefix common factor not answerable
+                             from the suffix array, 4 K-band bound, 5 exons not in order; 0 with PGPU_OK */
+  uint8_t  verdict;       /* 0 kept; 1 emptied by clean_noisy_exons, 2 by clean_external_exons */
+  uint8_t  prefix_added;  /* 1: search_small_exon_at_prefix inserted an exon */
+  uint8_t  reserved;
+  uint32_t n_added;       /* exons inserted by steps 1 and 2 together */
+  uint32_t n_list;        /* exons of the list after step 2, written at out_exons[2 * first_exon ..) */
+  uint32_t first_kept, n_kept;   /* the run step 3 keeps, relative to that list; 0, 0 unless verdict 0 */
+} pgpu_small_result;      /* 24 bytes, no padding */
+
+/* The three steps.  `est` and `orig` are the two sequences of the query; G is the resident sequence, gl its length; MIL is
+ * params->min_intron_length.  The list grows, so out_exons and out_steps have 2 * n_exons_total entries: a query writes its
+ * list at 2 * first_exon (queries share no exon, so the lists do not meet), and every slot no query fills is written as 0.
+ *  - Step 1, search_small_exon_at_prefix (:500-606), on est, only when the first exon p1 has EST_start > 6.  With e1len,
+ *    g1len the exon's two lengths: nothing happens unless e1len + p1.EST_start >= 6 + 23 (:517).  eplen = min(p1.EST_start,
+ *    p1.GEN_start, 46), epfact = est + p1.EST_start - eplen.  (cflen, pg, pe) = find_longest_common_factor_dp(G[0 ..
+ *    p1.GEN_start), epfact): PGPU_DP_LCF's answer -- longest, then smallest start in G, then in the EST piece, N a wildcard.
+ *    cflen < 6: nothing happens.  edp = the edit distance of the exon's first min(e1len, g1len, 23) bytes on est and on G
+ *    (PGPU_DP_ED's answer; 0 without a DP when the strings are equal), computed only when cflen >= 6.  `pe` is an offset
+ *    inside epfact, and the reference uses it as an absolute EST coordinate from here on (:549-603); so does this entry:
+ *    allelen = min(p1.EST_end + 1, p1.EST_start + 23) - pe, allglen = min(p1.GEN_end + 1, p1.GEN_start + 23) - pg, both
+ *    long when EST_start > 46.  allelen < 12: nothing happens (the host code's return: general_refine_borders has no cut
+ *    to try).  Otherwise general_refine_borders(est + pe, allelen, G + pg, allglen) with p0 = 6, p1 = allelen - 6, max_errs =
+ *    edp and tail = min(2, gl - (pg + allglen)): PGPU_DP_BORDERS's answer; only the first and last min(allelen + edp,
+ *    allglen) genomic bytes are read.  Then the four tests of :568-583 in order: the refinement is ok; (int)off_t2 -
+ *    (int)off_t1 >= MIL (the raw value, as int); G[pg + off_t1 ..] begins GT and G[.. pg + off_t2 - 1] ends AG, or gt and ag
+ *    (is_canonical_intron :481-494: no mixed case, no GC; with MIL <= 0 the two pairs can lie in front of G, where the
+ *    reference reads outside its string: here a byte outside G is no match); off_p - pe >= 6 in unsigned arithmetic (so
+ *    off_p < pe passes).
+ *    The new exon (pe, pe + off_p - 1, pg, pg + off_t1 - 1) goes in front of p1, and p1.EST_start = pe + off_p,
+ *    p1.GEN_start = pg + off_t2.
+ *  - Step 2, search_small_exon (:641-871), on est, for every adjacent pair (p1, p2) left to right; after an insertion the
+ *    walk goes on with (the old p2, its successor): the new exon is never analysed.  Nothing happens unless e1len + e2len
+ *    >= 6 + 2 * 23 (:664).  e1slen = min(e1len, g1len, 23): the last e1slen bytes of p1 on est and on G; e2plen = min(e2len,
+ *    g2len, 23): the first e2plen bytes of p2 on both.  sed and ped are the two edit distances (0 for equal strings, else
+ *    PGPU_DP_ED).  The search goes on only when sed + ped > 2 or classify(p1.GEN_end + 1, p2.GEN_start - 1) == 2
+ *    (pgpu_index_classify's answer).  A side whose distance is > 0 asks find_longest_common_factor_dp of its two strings
+ *    (EST piece first; PGPU_DP_LCF's answer) for (f1slen, e1socc, g1socc) or (f2plen, e2pocc, g2pocc); a side with distance
+ *    0 has its whole length and 0, 0.  The extension loop of :725-737 as written.  elen = (e1slen - e1socc) + (e2pocc +
+ *    f2plen) - 12, estart = p1.EST_end + 1 - e1slen + e1socc + 6, allgstart = p1.GEN_end + 1 - e1slen + g1socc + 6, allglen =
+ *    p2.GEN_start + g2pocc + f2plen - 6 - allgstart.  Then exactly one pgpu_sexon_query: (est + estart, elen, allgstart,
+ *    allglen, f1slen, f2plen, max(4, MIL) as int) through the search of pgpu_index_small_exons, which holds the four gates
+ *    of :743-758; the window ends inside p2, so it cannot pass the end of G; an elen below 0 finds nothing (an exon shorter than a
+ *    border whose match the loop of :725-737 lengthened: the reference's unsigned elen wraps and its copy leaves the EST).  A result of length >= 6 is accepted with the four cut
+ *    assignments of :836-866: the new exon (estart + offstart, .. + len - 1, gpos, gpos + len - 1) goes between p1 and p2,
+ *    p1.EST_end = estart + offstart - 1, p1.GEN_end = allgstart + offstart - 1, p2.EST_start = estart + offstart + len,
+ *    p2.GEN_start = allgstart + allglen - offend.
+ *  - Step 3, clean_factorizations (:914-950), on orig: step 5 of pgpu_index_clean_chains over the whole list
+ *    (clean_noisy_exons with only_internals = false: per exon K_band_edit_distance with the bound of its genomic length, an
+ *    exon with GEN_start > GEN_end counted as noisy, then the best-run rule), verdict 1 when nothing is left; then step 3
+ *    of pgpu_index_clean_chains on the run that is left (clean_external_exons: byte comparison for "distance > 0"), verdict
+ *    2 when nothing is left.  In this order, which is not that entry's.
+ *  - out_steps, per exon of the list: bit 0 inserted by step 1; bit 1 inserted by step 2; bit 2 an end of this exon was
+ *    moved by an insertion beside it; bit 4 the K-band verdict of step 3 was false; bit 5 dropped by clean_external_exons.
+ *  - Refusals are per query: PGPU_ERANGE and `refused`, every other field 0, the query's exons copied unchanged to
+ *    out_exons[2 * first_exon ..) with steps 0.  A cap refuses only when the computation it bounds would run.  1: more than
+ *    PGPU_SMALL_MAX_EXONS exons.  2: step 1 reaches its border refinement with allelen > PGPU_SMALL_MAX_PREFIX_WINDOW.  3:
+ *    step 1 reaches its common factor and the suffix array cannot answer it: p1.GEN_start beyond the first byte of G that
+ *    is no upper-case A, C, G or T (an exon that begins ON that byte is answered: the intron step 1 tests may lie at or
+ *    behind p1.GEN_start, lower case included), or a byte of epfact that is none of those, other than a single N or n.  4: step 3 meets
+ *    an exon with GEN_start <= GEN_end whose bound exceeds PGPU_SMALL_MAX_KBAND.  5: an exon with start > end, or two
+ *    adjacent exons that are not strictly increasing (p1 end < p2 start) on either string -- the reference asserts this
+ *    (:512-513, :655-658), and step 5 of pgpu_index_tail_chains can hand over such a list.
+ *  - PGPU_EINVAL for the whole call: what pgpu_index_tail_chains lists, with its coordinate rule, and params == NULL or
+ *    params->reserved != 0.
+ *  - n == 0 is PGPU_OK (out_exons and out_steps all 0).  idx may be built or loaded; the classification tables are built
+ *    on first use as for pgpu_index_small_exons. */
+int pgpu_index_small_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                            const pgpu_factor* exons, size_t n_exons_total, const pgpu_small_query* q, size_t n,
+                            const pgpu_small_params* params,
+                            pgpu_factor* out_exons /* 2 * n_exons_total */, uint8_t* out_steps /* 2 * n_exons_total */,
+                            pgpu_small_result* out);
+/* HIP-event time of the kernel of the calling thread's last pgpu_index_small_chains on a context with timing on
+ * (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_small_chains_kernel_ms(void);
+
 /* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
 /* of every pattern, the maximal pairings (p, t, l) of the pattern with the genomic, after the  */

@@ -112,6 +112,19 @@ class TailResult(C.Structure):     # pgpu_tail_result
                 ("recovered", C.c_uint8), ("n_kept", C.c_uint32), ("tail_added", C.c_uint32)]
 
 
+SmallQuery = TailQuery             # pgpu_small_query: est_off the working sequence, orig_off the original one
+
+
+class SmallParams(C.Structure):    # pgpu_small_params
+    _fields_ = [("min_intron_length", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class SmallResult(C.Structure):    # pgpu_small_result
+    _fields_ = [("status", C.c_int32), ("refused", C.c_uint8), ("verdict", C.c_uint8), ("prefix_added", C.c_uint8),
+                ("reserved", C.c_uint8), ("n_added", C.c_uint32), ("n_list", C.c_uint32), ("first_kept", C.c_uint32),
+                ("n_kept", C.c_uint32)]
+
+
 class CandParams(C.Structure):     # pgpu_cand_params
     _fields_ = [("min_factor_len", C.c_uint32), ("min_intron_length", C.c_int32)]
 
@@ -161,6 +174,11 @@ TAIL_UB_MED_EXON, TAIL_AFFIXES_LENGTH = 100, 5
 TAIL_QUERY_DTYPE = GAPS_QUERY_DTYPE + [("orig_off", "<u8")]
 TAIL_RESULT_DTYPE = [("status", "<i4"), ("verdict", "u1"), ("polyA", "u1"), ("polyadenil", "u1"), ("recovered", "u1"),
                      ("n_kept", "<u4"), ("tail_added", "<u4")]
+SMALL_MAX_EXONS, SMALL_MAX_PREFIX_WINDOW, SMALL_MAX_KBAND = 64, 256, 31
+SMALL_QUERY_DTYPE = TAIL_QUERY_DTYPE
+SMALL_PARAMS_DTYPE = [("min_intron_length", "<i4"), ("reserved", "<u4")]
+SMALL_RESULT_DTYPE = [("status", "<i4"), ("refused", "u1"), ("verdict", "u1"), ("prefix_added", "u1"), ("reserved", "u1"),
+                      ("n_added", "<u4"), ("n_list", "<u4"), ("first_kept", "<u4"), ("n_kept", "<u4")]
 CAND_NONE, CAND_NOT_PATH, CAND_REFUSED, CAND_ONE = range(4)
 MEG_TOO_COMPLEX, MEG_UNAVAILABLE = 1, 2
 CAND_PARAMS_DTYPE = [("min_factor_len", "<u4"), ("min_intron_length", "<i4")]
@@ -185,6 +203,7 @@ assert C.sizeof(ChainQuery) == 40 and C.sizeof(ChainResult) == 16
 assert C.sizeof(CleanQuery) == 32 and C.sizeof(CleanResult) == 16
 assert C.sizeof(GapsQuery) == 24 and C.sizeof(GapsResult) == 16
 assert C.sizeof(TailQuery) == 32 and C.sizeof(TailResult) == 16
+assert C.sizeof(SmallParams) == 8 and C.sizeof(SmallResult) == 24
 assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
 assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
 
@@ -199,6 +218,7 @@ EXPORTS = [
     "pgpu_index_clean_chains", "pgpu_index_clean_chains_kernel_ms",
     "pgpu_index_gap_chains", "pgpu_index_gap_chains_kernel_ms",
     "pgpu_index_tail_chains", "pgpu_index_tail_chains_kernel_ms",
+    "pgpu_index_small_chains", "pgpu_index_small_chains_kernel_ms",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -279,6 +299,11 @@ def lib():
                                              C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(TailResult)]
         L.pgpu_index_tail_chains_kernel_ms.argtypes = []
         L.pgpu_index_tail_chains_kernel_ms.restype = C.c_double
+        L.pgpu_index_small_chains.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(SmallQuery), sz,
+                                              C.POINTER(SmallParams), C.POINTER(Factor), C.POINTER(C.c_uint8),
+                                              C.POINTER(SmallResult)]
+        L.pgpu_index_small_chains_kernel_ms.argtypes = []
+        L.pgpu_index_small_chains_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
         L.pgpu_pairing_plan_meg_bytes.argtypes = [vp]
         L.pgpu_pairing_plan_meg_bytes.restype = u64
@@ -590,6 +615,35 @@ class Index:
 
     def tail_chains_kernel_ms(self):
         return self.ctx.L.pgpu_index_tail_chains_kernel_ms()
+
+    def small_chains_raw(self, ests: bytes, exons, queries, n: int, min_intron_length: int, params_reserved: int = 0,
+                         no_params: bool = False):
+        """One pgpu_index_small_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+        SMALL_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of SMALL_RESULT_DTYPE); the two
+        output arrays have 2 * len(exons) entries, a query's list at 2 * first_exon."""
+        import numpy as np
+        out_exons = np.zeros(2 * len(exons), dtype=np.dtype(FACTOR_DTYPE))
+        out_steps = np.zeros(2 * len(exons), dtype=np.uint8)
+        res = np.zeros(n, dtype=np.dtype(SMALL_RESULT_DTYPE))
+        prm = SmallParams(min_intron_length, params_reserved)
+        rc = self.ctx.L.pgpu_index_small_chains(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)),
+                                                len(exons), queries.ctypes.data_as(C.POINTER(SmallQuery)), n,
+                                                None if no_params else C.byref(prm),
+                                                out_exons.ctypes.data_as(C.POINTER(Factor)),
+                                                out_steps.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                res.ctypes.data_as(C.POINTER(SmallResult)))
+        return rc, out_exons, out_steps, res
+
+    def small_chains(self, ests: bytes, exons, queries, min_intron_length: int):
+        """The last steps of the reference's refine_EST_factorizations over every factorization `queries` names (a new small
+        exon in front of the first exon and between every two, then the last cleaning on the original sequence, chained on
+        the device): (out_exons, out_steps, results) as numpy arrays, the first two of 2 * len(exons) entries."""
+        rc, out_exons, out_steps, res = self.small_chains_raw(ests, exons, queries, len(queries), min_intron_length)
+        self.ctx.check(rc)
+        return out_exons, out_steps, res
+
+    def small_chains_kernel_ms(self):
+        return self.ctx.L.pgpu_index_small_chains_kernel_ms()
 
     def candidates_raw(self, records: bytes, rec_first, n: int, min_factor_len, min_intron_length, exons_cap: int):
         """One pgpu_index_candidates call as it is: `records` the concatenated MEG records, `rec_first` a numpy uint64 array

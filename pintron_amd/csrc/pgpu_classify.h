@@ -17,6 +17,9 @@
 #include "pgpu_find.h"
 
 struct ClassView { const uint8_t* cls_start; const uint8_t* cls_end; uint32_t n; };
+// The view of an index's tables for a kernel of another file (pgpu_classify.hip): they are built now, on the context's
+// bound device and stream, when nobody has asked before.  PGPU_OK, or the failed context's code.
+int pgpu_class_view_get(pgpu_ctx* ctx, const pgpu_index* idx, ClassView* out);
 
 enum { CLS_P5_GT = 1, CLS_P5_GC = 2, CLS_P5_AT = 3, CLS_P3_AG = 1, CLS_P3_AC = 2 };
 

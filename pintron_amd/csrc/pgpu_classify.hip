@@ -225,6 +225,13 @@ thread_local double t_sexon_ms = 0.0;
 
 }  // namespace
 
+int pgpu_class_view_get(pgpu_ctx* ctx, const pgpu_index* idx, ClassView* out) {
+  const ClassTables* t = nullptr;
+  const int rc = class_tables_get(ctx, idx, &t);
+  if (rc == PGPU_OK) *out = class_view(t);
+  return rc;
+}
+
 extern "C" double pgpu_index_small_exons_kernel_ms(void) { return t_sexon_ms; }
 
 extern "C" int pgpu_index_classify(pgpu_ctx* ctx, const pgpu_index* idx, const pgpu_intron* introns, size_t n, uint8_t* out_type) {

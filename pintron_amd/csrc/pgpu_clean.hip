@@ -23,6 +23,7 @@
 #include "pgpu_internal.h"
 #include "pgpu_query_call.h"
 #include "pgpu_wave_dp.h"
+#include "pgpu_clean_body.h"
 #include "pgpu_stage_launch.h"
 
 namespace {
@@ -52,27 +53,7 @@ struct MemRows {
   __device__ __forceinline__ void set_g(uint32_t q, uint32_t v) { ga[q] = (uint8_t)v; }
 };
 
-// update_with_subfact_with_best_coverage (:1900-1987) on the run [lo, hi) with the exons of `bad` flagged: the run of
-// unflagged exons with the largest cover on the EST, the first of equals; lo == hi when none is left
-__device__ __forceinline__ void best_run(const pgpu_factor* ex, unsigned long long bad, uint32_t& lo, uint32_t& hi) {
-  if (!bad) return;
-  int best_cover = -1;
-  uint32_t best_lo = 0, best_hi = 0, left = lo;
-  while (bad) {
-    const uint32_t r = (uint32_t)__builtin_ctzll(bad);
-    bad &= bad - 1ull;
-    if (left < r) {
-      const int cover = ex[r - 1].EST_end - ex[left].EST_start + 1;
-      if (cover > best_cover) { best_cover = cover; best_lo = left; best_hi = r; }
-    }
-    left = r + 1;
-  }
-  if (left < hi) {
-    const int cover = ex[hi - 1].EST_end - ex[left].EST_start + 1;
-    if (cover > best_cover) { best_cover = cover; best_lo = left; best_hi = hi; }
-  }
-  lo = best_lo; hi = best_hi;
-}
+// (best_run, the best-run rule of steps 4 and 5, and external_exon_ok, the test of step 3: pgpu_clean_body.h)
 
 __global__ __launch_bounds__(64)
 void clean_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __restrict__ ests, const pgpu_factor* __restrict__ exons,
@@ -84,8 +65,6 @@ void clean_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __re
   const size_t ws_wave = (ws_dirs + ws_rows + sizeof(DevResult) + 255) & ~(size_t)255;
   uint8_t* const w = ws + (size_t)blockIdx.x * ws_wave;
   DevResult* const res = reinterpret_cast<DevResult*>(w + ws_dirs + ws_rows);
-  // a genomic byte for the splice sites: upper case, 0 outside the sequence
-  auto site = [&](int i) -> uint32_t { return (i >= 0 && (uint32_t)i < n) ? ((uint32_t)T[i] & ~32u) : 0u; };
   for (uint32_t c = blockIdx.x; c < n_queries; c += gridDim.x) {
     const pgpu_clean_query q = queries[c];
     const uint8_t* const est = ests + q.est_off;
@@ -196,27 +175,7 @@ void clean_kernel(const uint8_t* __restrict__ T, uint32_t n, const uint8_t* __re
     // ---- step 3: clean_external_exons (:1706-1825)
     for (uint32_t end = 0; end < 2 && !refused && cr.verdict == 0; ++end) {
       const uint32_t at = end == 0 ? lo : hi - 1;
-      const pgpu_factor f = S.ex[at];
-      const int gl = f.GEN_end - f.GEN_start + 1, el = f.EST_end - f.EST_start + 1;
-      bool ok = gl >= 10;
-      if (ok && gl < 20) {
-        if (hi - lo < 2) ok = false;                                       // no neighbour to share an intron with
-        else if (end == 0) {
-          const int acc = S.ex[lo + 1].GEN_start;
-          ok = site(f.GEN_end + 1) == 'G' && (site(f.GEN_end + 2) == 'T' || site(f.GEN_end + 2) == 'C') &&
-               site(acc - 2) == 'A' && site(acc - 1) == 'G';
-        } else {
-          const int don = S.ex[hi - 2].GEN_end;
-          ok = site(f.GEN_start - 2) == 'A' && site(f.GEN_start - 1) == 'G' &&
-               site(don + 1) == 'G' && (site(don + 2) == 'T' || site(don + 2) == 'C');
-        }
-        // an edit distance > 0: the two pieces differ as byte strings
-        if (ok) {
-          bool differ = gl != el;
-          if (!differ && (int)lane < gl) differ = T[f.GEN_start + (int)lane] != est[f.EST_start + (int)lane];
-          ok = !__any(differ);
-        }
-      }
+      const bool ok = external_exon_ok(T, n, est, S.ex, lo, hi, end, lane);
       if (!ok) {
         if (lane == 0) S.marks[at] |= 2u;
         if (end == 0) ++lo; else --hi;

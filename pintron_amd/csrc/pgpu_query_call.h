@@ -1,8 +1,8 @@
-// The host side of a query on the resident index, once: what the eight entries pgpu_index_find, pgpu_index_classify,
+// The host side of a query on the resident index, once: what the nine entries pgpu_index_find, pgpu_index_classify,
 // pgpu_index_small_exons, pgpu_index_refine_introns, pgpu_index_refine_chains, pgpu_index_clean_chains,
-// pgpu_index_gap_chains and pgpu_index_tail_chains share around their kernels.  An entry validates, lays out its device block, copies in, launches,
+// pgpu_index_gap_chains, pgpu_index_tail_chains and pgpu_index_small_chains share around their kernels.  An entry validates, lays out its device block, copies in, launches,
 // copies out and waits, as straight-line code; the QueryCall on its stack owns what has to be given back whichever way the
-// entry returns.  The four chained entries (one query = one list of exons, chained on the device) share more: the chained
+// entry returns.  The five chained entries (one query = one list of exons, chained on the device) share more: the chained
 // path at the end.
 //
 // The contract of every entry (tests/test_gpu_query_calls.py): a refused call and an empty one leave the entry's
@@ -85,12 +85,13 @@ struct QueryCall {
     if (e_ != hipSuccess) return call.fail(e_);         \
   } while (0)
 
-// ---- The chained path: pgpu_index_refine_chains, pgpu_index_clean_chains, pgpu_index_gap_chains and
-// pgpu_index_tail_chains.  Their query structs
+// ---- The chained path: pgpu_index_refine_chains, pgpu_index_clean_chains, pgpu_index_gap_chains,
+// pgpu_index_tail_chains and pgpu_index_small_chains.  Their query structs
 // begin with est_off, est_len, first_exon, n_exons and reserved; the calls answer with out_exons and one byte per exon,
 // parallel to `exons` (an exon no query names: a copy and byte 0; an empty call: that for every exon, without a device
-// call), and with one result per query.  An entry keeps what the others do differently: its own rules, its workspace and
-// its kernel.
+// call), and with one result per query.  An entry whose lists grow (pgpu_index_small_chains) has `out_per_exon` = 2 output
+// slots per input exon: a query's list is at out_per_exon * first_exon, and what no query fills is 0 instead of a copy.
+// An entry keeps what the others do differently: its own rules, its workspace and its kernel.
 
 // which exons a query has named already; calloc, for no exception may cross the C boundary
 struct NamedExons { uint8_t* p = nullptr; ~NamedExons() { free(p); } };
@@ -115,18 +116,20 @@ bool chained_queries_ok(const Query* q, size_t n, size_t ests_len, const pgpu_fa
 }
 
 // The one device block: [ests + 64 | exons | queries | out exons | one byte per exon | results | (extra) | workspace],
-// every part at a multiple of 256 (`extra_bytes`, clean's flag slot, is 0 or 256).  The sizes are the unrounded ones.
+// every part at a multiple of 256 (`extra_bytes`, clean's flag slot, is 0 or 256).  The sizes are the unrounded ones; the
+// two output parts hold out_per_exon entries per exon.
 struct ChainedLayout {
-  size_t ests_len, ex_bytes, q_bytes, n_exons, r_bytes;
+  size_t ests_len, ex_bytes, q_bytes, n_exons, r_bytes, out_per_exon;
   size_t exons, queries, out_exons, out_bytes, results, extra, ws, total;      // the ESTs are at 0
 };
 inline ChainedLayout chained_layout(size_t ests_len, size_t n_exons_total, size_t n, size_t query_size, size_t result_size,
-                                    size_t extra_bytes, size_t ws_bytes) {
+                                    size_t extra_bytes, size_t ws_bytes, size_t out_per_exon = 1) {
   ChainedLayout L;
+  L.out_per_exon = out_per_exon;
   L.ests_len = ests_len; L.ex_bytes = n_exons_total * sizeof(pgpu_factor); L.q_bytes = n * query_size;
   L.n_exons = n_exons_total; L.r_bytes = n * result_size;
   L.exons = up256(ests_len + 64); L.queries = L.exons + up256(L.ex_bytes); L.out_exons = L.queries + up256(L.q_bytes);
-  L.out_bytes = L.out_exons + up256(L.ex_bytes); L.results = L.out_bytes + up256(n_exons_total);
+  L.out_bytes = L.out_exons + up256(out_per_exon * L.ex_bytes); L.results = L.out_bytes + up256(out_per_exon * n_exons_total);
   L.extra = L.results + up256(L.r_bytes); L.ws = L.extra + extra_bytes; L.total = L.ws + ws_bytes;
   return L;
 }
@@ -136,7 +139,7 @@ inline ChainedLayout chained_layout(size_t ests_len, size_t n_exons_total, size_
 constexpr int CHAINED_GO = 1;          // every PGPU_* code is <= 0
 inline int chained_begin(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len, const pgpu_factor* exons,
                          size_t n_exons_total, const void* q, size_t n, pgpu_factor* out_exons, uint8_t* out_bytes,
-                         const void* out, const char* what, NamedExons& named) {
+                         const void* out, const char* what, NamedExons& named, size_t out_per_exon = 1) {
   if (!ctx || !idx || (n && (!q || !out)) || (ests_len && !ests) || (n_exons_total && (!exons || !out_exons || !out_bytes)))
     return PGPU_EINVAL;
   const auto fail = [&](int code, const char* text) {
@@ -148,7 +151,9 @@ inline int chained_begin(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests,
   named.p = (uint8_t*)calloc(n_exons_total ? n_exons_total : 1, 1);
   if (!named.p) return fail(PGPU_ENOMEM, "no memory for the table of the exons the %s name");
   if (n) return CHAINED_GO;
-  if (n_exons_total) { memcpy(out_exons, exons, n_exons_total * sizeof(pgpu_factor)); memset(out_bytes, 0, n_exons_total); }
+  if (n_exons_total && out_per_exon == 1) memcpy(out_exons, exons, n_exons_total * sizeof(pgpu_factor));
+  if (n_exons_total && out_per_exon != 1) memset(out_exons, 0, out_per_exon * n_exons_total * sizeof(pgpu_factor));
+  if (n_exons_total) memset(out_bytes, 0, out_per_exon * n_exons_total);
   return PGPU_OK;
 }
 
@@ -170,14 +175,16 @@ inline hipError_t chained_upload(const QueryCall& call, const ChainedLayout& L, 
   hipError_t e = L.ests_len ? hipMemcpyAsync(call.d, ests, L.ests_len, hipMemcpyHostToDevice, call.st) : hipSuccess;
   if (e == hipSuccess) e = hipMemcpyAsync(call.d + L.exons, exons, L.ex_bytes, hipMemcpyHostToDevice, call.st);
   if (e == hipSuccess) e = hipMemcpyAsync(call.d + L.queries, q, L.q_bytes, hipMemcpyHostToDevice, call.st);
-  if (e == hipSuccess) e = hipMemcpyAsync(call.d + L.out_exons, call.d + L.exons, L.ex_bytes, hipMemcpyDeviceToDevice, call.st);
-  if (e == hipSuccess) e = hipMemsetAsync(call.d + L.out_bytes, 0, L.n_exons, call.st);
+  if (e == hipSuccess && L.out_per_exon == 1)
+    e = hipMemcpyAsync(call.d + L.out_exons, call.d + L.exons, L.ex_bytes, hipMemcpyDeviceToDevice, call.st);
+  if (e == hipSuccess && L.out_per_exon != 1) e = hipMemsetAsync(call.d + L.out_exons, 0, L.out_per_exon * L.ex_bytes, call.st);
+  if (e == hipSuccess) e = hipMemsetAsync(call.d + L.out_bytes, 0, L.out_per_exon * L.n_exons, call.st);
   return e;
 }
 inline hipError_t chained_download(const QueryCall& call, const ChainedLayout& L, pgpu_factor* out_exons, uint8_t* out_bytes,
                                    void* out) {
-  hipError_t e = hipMemcpyAsync(out_exons, call.d + L.out_exons, L.ex_bytes, hipMemcpyDeviceToHost, call.st);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_bytes, call.d + L.out_bytes, L.n_exons, hipMemcpyDeviceToHost, call.st);
+  hipError_t e = hipMemcpyAsync(out_exons, call.d + L.out_exons, L.out_per_exon * L.ex_bytes, hipMemcpyDeviceToHost, call.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_bytes, call.d + L.out_bytes, L.out_per_exon * L.n_exons, hipMemcpyDeviceToHost, call.st);
   if (e == hipSuccess) e = hipMemcpyAsync(out, call.d + L.results, L.r_bytes, hipMemcpyDeviceToHost, call.st);
   return e;
 }

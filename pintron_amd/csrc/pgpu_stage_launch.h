@@ -1,6 +1,7 @@
-// The chained stage kernels (clean_kernel, gaps_kernel, chain_kernel, tail_kernel) as plain launches over device pointers,
+// The chained stage kernels (clean_kernel, gaps_kernel, chain_kernel, tail_kernel, small_kernel) as plain launches over device pointers,
 // for a caller that has the ESTs, the exons and the queries in HBM already: the factorization driver of pgpu_fact.hip (which
-// does not append the tail stage yet).  Each of pgpu_clean.hip, pgpu_gaps.hip, pgpu_chain.hip and pgpu_tail.hip launches its
+// does not append the tail and small stages yet).  Each of pgpu_clean.hip, pgpu_gaps.hip, pgpu_chain.hip, pgpu_tail.hip and
+// pgpu_small.hip launches its
 // kernel through the function below from its public entry too, so there is one launch per kernel.  Beside them the one rule of a public entry that the driver has to repeat on
 // the device: what an end exon of a clean query asks of the per-wave workspace (clean_query_need), __host__ __device__ so
 // that the entry's validator and the driver's hand-off kernel run the same code.
@@ -10,6 +11,9 @@
 #include <stdint.h>
 
 #include "../../include/pintron_gpu.h"
+#include "pgpu_index.h"
+
+struct ClassView;          // pgpu_classify.h
 
 // direction bytes of one end-exon alignment, as the plan builder sizes them: lev_wave<ALIGN> [step][64 lanes] of 1 B,
 // align_band [row / 16][64 lanes] of 4 B
@@ -74,3 +78,8 @@ void pgpu_chain_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, con
 // pgpu_tail.hip: no workspace; tlen is the length of the resident sequence T
 void pgpu_tail_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, const pgpu_factor* exons, const pgpu_tail_query* q,
                       uint32_t n, size_t waves, pgpu_factor* out_exons, uint8_t* out_steps, pgpu_tail_result* out, hipStream_t st);
+// pgpu_small.hip: no workspace; the views of the resident index (pgpu_index_lcf_view) and of its classification tables
+// (pgpu_class_view_get); out_exons and out_steps hold two entries per exon of `exons`
+void pgpu_small_launch(const LcfIndexView& ix, const ClassView& cv, const uint8_t* ests, const pgpu_factor* exons,
+                       const pgpu_small_query* q, uint32_t n, int min_intron_length, size_t waves, pgpu_factor* out_exons,
+                       uint8_t* out_steps, pgpu_small_result* out, hipStream_t st);

@@ -1320,3 +1320,44 @@ ef_est* ef_get_est_factorizations(const ef_seq* est_info, ef_meg* V, const ef_co
   est->factorizations = flist;
   return est;
 }
+
+/* One factorization through the last steps of ef_refine_est_factorizations (ef_factref.c: ef_refine_last_steps):
+ * search_new_small_exons on EST, the working sequence, and clean_factorizations on ORIG, the original one -- what
+ * pgpu_index_small_chains computes on the device (include/pintron_gpu.h).  `gen` carries the 6-mer index and the
+ * classification tables of its sequence.  exons: n_exons in, room for cap (the list can grow to 2 * n_exons); at most cap are
+ * written back and *n_out is the number left.  Returns 1 when the cleaning emptied the list (*n_out = 0), else 0.
+ * est-fact does not call this (cold, behind everything else in this file). */
+__attribute__((cold)) unsigned ef_chain_small(const char* EST, const char* ORIG, const ef_seq* gen, const ef_config* cfg, ef_backend* be,
+                        ef_factor* exons, unsigned n_exons, unsigned cap, unsigned* n_out) {
+  ef_seq est_info;
+  memset(&est_info, 0, sizeof est_info);
+  est_info.seq = (char*)EST; est_info.original_seq = (char*)ORIG;
+  ef_list* f = efl_new();
+  for (unsigned k = 0; k < n_exons; ++k) {
+    ef_factor* x = (ef_factor*)malloc(sizeof(ef_factor));
+    *x = exons[k];
+    efl_push_back(f, x);
+  }
+  ef_est e;
+  memset(&e, 0, sizeof e);
+  e.info = &est_info;
+  e.factorizations = efl_new();
+  efl_push_back(e.factorizations, f);
+  ef_refine_last_steps(gen, &e, cfg, be);
+  *n_out = 0;
+  if (!efl_empty(e.factorizations)) {
+    ef_iter it = efl_begin((ef_list*)efl_head(e.factorizations));
+    while (efi_has_next(&it)) {
+      const ef_factor* x = (const ef_factor*)efi_next(&it);
+      if (*n_out < cap) exons[*n_out] = *x;
+      ++*n_out;
+    }
+  }
+  efl_free(e.factorizations, ef_factorization_free);
+  return *n_out == 0 ? 1u : 0u;
+}
+
+/* config->min_intron_length for a caller that holds the configuration as bytes (the tests of ef_chain_small) */
+__attribute__((cold)) void ef_config_set_min_intron_length(ef_config* cfg, int min_intron_length) {
+  cfg->min_intron_length = min_intron_length;
+}

@@ -546,7 +546,7 @@ static void search_new_small_exons(const ef_seq* gen, ef_est* e, const ef_config
 }
 
 /* clean_factorizations (:914-950): cleaning on the ORIGINAL EST sequence */
-static void clean_factorizations(const ef_seq* gen, ef_est* e, const ef_config* cfg, ef_backend* be) {
+static inline __attribute__((always_inline)) void clean_factorizations(const ef_seq* gen, ef_est* e, const ef_config* cfg, ef_backend* be) {
   ef_list* cleaned = efl_new();
   ef_iter it = efl_begin(e->factorizations);
   while (efi_has_next(&it)) {
@@ -593,4 +593,13 @@ void ef_refine_est_factorizations(const ef_seq* gen, ef_est* e, const ef_config*
   ef_phase(EFP_REF_CLEAN);
   clean_factorizations(gen, e, cfg, be);
   ef_phase(EFP_FACTREF);
+}
+
+/* The steps of ef_refine_est_factorizations that concern one factorization alone and come last: search_new_small_exons and
+ * clean_factorizations (whose add_if_not_exists has nothing to compare one factorization with).  For ef_chain_small
+ * (ef_fact.c); est-fact does not call this: it is kept out of the way of the code that runs (cold, behind everything else;
+ * clean_factorizations stays inlined into its one caller on est-fact's path, as it was when that was its only caller). */
+__attribute__((cold)) void ef_refine_last_steps(const ef_seq* gen, ef_est* e, const ef_config* cfg, ef_backend* be) {
+  search_new_small_exons(gen, e, cfg, be);
+  clean_factorizations(gen, e, cfg, be);
 }

@@ -425,6 +425,14 @@ unsigned ef_chain_factorization(const void* rec, const ef_config* cfg, const cha
  * answers on the device; est-fact does not call it */
 unsigned ef_chain_tail(const char* EST, const char* ORIG, const char* GEN, struct ef_backend* be, ef_factor* exons, unsigned n_exons,
                        unsigned* n_out, unsigned* polyA, unsigned* polyadenil);
+/* one factorization through the last steps of ef_refine_est_factorizations: search_new_small_exons on EST and
+ * clean_factorizations on ORIG (ef_fact.c).  `gen` is the genomic record with its 6-mer index and its classification
+ * tables (ef_seq_index_kmers, ef_classify_prepare).  exons: n_exons in, room for cap; at most cap are written back and
+ * *n_out is the number left, 0 when the cleaning emptied the list (the return value is 1 then, else 0).  What
+ * pgpu_index_small_chains answers on the device; est-fact does not call it */
+unsigned ef_chain_small(const char* EST, const char* ORIG, const ef_seq* gen, const ef_config* cfg, struct ef_backend* be,
+                        ef_factor* exons, unsigned n_exons, unsigned cap, unsigned* n_out);
+void ef_config_set_min_intron_length(ef_config* cfg, int min_intron_length);
 /* a factorization = ef_list of ef_factor*; a list of factorizations = ef_list of ef_list* */
 
 typedef struct {
@@ -447,6 +455,8 @@ void ef_refine_est_factorizations(const ef_seq* gen, ef_est* e, const ef_config*
 /* its first steps that concern one factorization alone (remove_invalid, recover_affixes, remove_false_small_exons), for
  * ef_chain_tail */
 void ef_refine_first_steps(const ef_seq* gen, ef_est* e, ef_backend* be);
+/* its last steps that concern one factorization alone (search_new_small_exons, clean_factorizations), for ef_chain_small */
+void ef_refine_last_steps(const ef_seq* gen, ef_est* e, const ef_config* cfg, ef_backend* be);
 void ef_remove_factorizations_with_very_small_exons(ef_list* facts);
 void ef_remove_duplicated_factorizations(ef_list* facts);
 /* refine_intron (src/refine-intron.c:47-265) */
