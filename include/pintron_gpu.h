@@ -653,7 +653,8 @@ int pgpu_pairings(pgpu_ctx* ctx, const pgpu_index* idx,
  * create uploads the patterns; run launches every kernel with the given parameters (may be
  * repeated with other parameters: the reference re-runs build_vertex_set with a longer
  * min_factor_len when a MEG is too complex, src/compute-est-fact.c:132-144); fetch downloads.
- * The stages of a plan build on each other -- run, run_meg, run_candidates, run_factorizations, below -- and the run
+ * The stages of a plan build on each other -- run, run_meg, run_candidates, run_factorizations,
+ * run_final_factorizations, below -- and the run
  * of a stage takes with it what the stages behind it had made.  On a plan with patterns a fetch whose stage's results
  * are not there (never made, or gone with a later run of an earlier stage) is PGPU_EINVAL with a message, never
  * stale data. */
@@ -897,6 +898,104 @@ int pgpu_index_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const char* 
 /* HIP-event time of the whole device part of the calling thread's last pgpu_index_factorizations on a context with timing
  * on (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_factorizations_kernel_ms(void);
+
+/* ------------------------------------------------------------------------------------------ */
+/* final factorizations -- the factorization stage above, then pgpu_index_tail_chains and      */
+/* pgpu_index_small_chains on what it left, in ONE call, nothing leaving HBM in between: for an */
+/* EST with exactly one candidate this ends with the factorization as refine_EST_factorizations */
+/* (src/factorization-refinement.c:1270-1305) leaves it, with the polyA flags and one verdict   */
+/* per EST.  The two stage kernels are the ones of the chained entries; between them one thread */
+/* per EST does what a caller of those entries does on the host: take out the exons the tail    */
+/* stage removed, build the next query, cut the kept run out of small's list.                   */
+/* remove_duplicated_factorizations, add_if_not_exists and ef_remove_factorizations_with_very_  */
+/* small_exons compare or filter whole factorizations and stay with the caller.  Nothing in the */
+/* library calls these entries yet.                                                             */
+/* ------------------------------------------------------------------------------------------ */
+typedef struct {
+  uint8_t  outcome;       /* PGPU_FACT_HOST / EMPTY / DONE */
+  uint8_t  stage;         /* 0-3 as pgpu_fact_result; 4 tail; 5 small */
+  uint16_t detail;        /* stages 0-3: pgpu_fact_result's. HOST at 4, 5: 1 a cap, 2 the validator. EMPTY at 4: 1;
+                             at 5: small's verdict 1 or 2. DONE: bit 0 = dropped_first */
+  uint32_t first_exon;    /* DONE only */
+  uint16_t n_exons;       /* DONE only, <= 128 */
+  uint16_t n_merged;      /* from gaps, whenever stage 3 said DONE */
+  uint32_t total_edit;    /* as pgpu_fact_result */
+  uint32_t tail_added;    /* whenever tail answered PGPU_OK, else 0 */
+  uint8_t  polyA, polyadenil, recovered;   /* the same */
+  uint8_t  refused;       /* HOST at stage 5, detail 1: pgpu_small_result.refused; else 0 */
+  uint16_t n_removed;     /* exons step 5 of tail removed */
+  uint16_t n_added;       /* exons small inserted */
+  uint16_t n_cleaned;     /* n_list - n_kept */
+  uint8_t  prefix_added, reserved;
+} pgpu_final_result;      /* 32 bytes, no padding: 0,1,2,4,8,10,12,16,20,21,22,23,24,26,28,30,31 */
+typedef pgpu_tail_query pgpu_final_query;   /* n_exons == 0: no candidate */
+
+/*  - The stages 0-3, per EST, are those of pgpu_fact_result; an EST that is HOST or EMPTY there keeps that outcome, stage
+ *    and detail, and total_edit.  An EST that is DONE at stage 3 goes on, each further stage exactly the chained entry of
+ *    that name on a query of its own, est_off the WORKING sequence and orig_off the ORIGINAL one:
+ *    4. tail on the refined exons.  What pgpu_index_tail_chains refuses for a whole call is HOST with detail 2 for this
+ *       EST: a coordinate that is no byte of what it indexes (the rule of stage 3 lets an end equal to a length pass, this
+ *       one does not; nothing known gets such a coordinate as far as stage 3, and the test stays).
+ *       PGPU_ERANGE is HOST with detail 1.  Verdict 1 is EMPTY, detail 1.  tail_added, polyA, polyadenil and recovered
+ *       are pgpu_tail_result's whenever that status is PGPU_OK, under verdict 1 too, and stay whatever stage 5 says;
+ *       n_removed = the query's exons - n_kept under verdict 0, else 0;
+ *    5. small, with params->min_intron_length, on the exons tail kept (out_steps bits 0-1 != 3), in their order.  What
+ *       pgpu_index_small_chains refuses for a whole call: HOST, detail 2.  PGPU_ERANGE: HOST, detail 1, with `refused`
+ *       that entry's code 1 .. 5.  Otherwise n_added, prefix_added and n_cleaned = n_list - n_kept are
+ *       pgpu_small_result's; verdict 1 or 2: EMPTY with that detail; verdict 0: DONE, detail bit 0 the dropped_first of
+ *       stage 3, and the factorization is the run [first_kept, first_kept + n_kept) of small's list.
+ *  - exons and steps of a call are compact, in EST order; only DONE has any.  steps[k] is pgpu_index_small_chains'
+ *    out_steps of that exon.  A call never has more than twice the candidates' exons.
+ *  - An outcome never depends on another EST of the call: an EST with nothing to do at a stage is given that stage's
+ *    trivial query on a placeholder exon of its own -- tail: (0, est_len - 1, 0, 0), which extends nothing, has no polyA
+ *    window, is valid, has no affix to recover and no neighbour; small: (0, 0, 0, 0), which has no prefix to search, no
+ *    pair, and a last cleaning of one cell (the one banded distance of step 3) whose verdict is ignored.  Beside that cell
+ *    neither asks a DP question, and neither can be refused.  An empty pattern of a plan (never DONE) has (0, -1, 0, 0) at
+ *    tail, which reads nothing and is verdict 1, unread. */
+
+/* A plan whose patterns are WORKING sequences (polyA/T masked) can hold the ORIGINAL ones of the few patterns where the
+ * two differ: orig_pat[0 .. n_orig) names those patterns, strictly ascending, and original k is orig_bytes[orig_first[k]
+ * .. orig_first[k + 1]), of exactly the length of pattern orig_pat[k].  The originals lie behind the pattern bytes in the
+ * same device allocation, with one offset per pattern into it (a pattern without an original: its own offset); they are
+ * not packed and take no part in the pairings.  resident != 0: as pgpu_pairing_plan_create_resident, else as
+ * pgpu_pairing_plan_create; those two are this call with n_orig == 0.  PGPU_EINVAL with a message: an index >= n_pat, a
+ * list that is not strictly ascending, a length that differs, a null pointer with n_orig > 0. */
+int pgpu_pairing_plan_create_with_originals(pgpu_ctx* ctx, const pgpu_index* idx, const char* patterns, const uint64_t* pat_off,
+                                            size_t n_pat, int resident, const uint32_t* orig_pat, const uint64_t* orig_first,
+                                            const char* orig_bytes, size_t n_orig, pgpu_pairing_plan** plan);
+
+/* Plan form: the answer of the last pgpu_pairing_plan_run_factorizations, where it lies; the ESTs are the plan's patterns
+ * and their originals.  The fifth stage of a plan: the factorizations stay fetchable and unchanged; a run of any earlier
+ * stage takes the finals with it.  PGPU_EINVAL (with a message): no run_factorizations since the last run of an earlier
+ * stage; the results of a resident plan were overwritten by the run of another one; params->reserved != 0; fetch before
+ * the run.  params == NULL is a bare PGPU_EINVAL.  An empty plan is PGPU_OK.  A rerun gives the same bytes.  The buffers
+ * come from where the MEG stage's do.  The one host wait of the call is its last statement (8 bytes: the exon count). */
+int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_small_params* params);
+uint64_t pgpu_pairing_plan_final_exons(const pgpu_pairing_plan* plan);   /* exons of the last run_final_factorizations */
+/* out: n_pat results; exons, steps: at least final_exons entries (PGPU_ENOSPC when cap is smaller) */
+int pgpu_pairing_plan_fetch_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_final_result* out,
+                                                 pgpu_factor* exons, uint8_t* steps, size_t cap);
+/* HIP-event times of the last run_final_factorizations: k = 0 the whole call (hand-off kernels and the scan included),
+ * 1 tail_kernel, 2 small_kernel; 0 without timing */
+double pgpu_pairing_plan_final_ms(const pgpu_pairing_plan* plan, int k);
+
+/* Index form: candidate -> clean -> gaps -> refine -> tail -> small for a caller that holds candidates.  One query = one
+ * EST: the fields of pgpu_tail_query, where n_exons == 0 means "no candidate" (HOST at stage 0, detail PGPU_CAND_NONE;
+ * first_exon is then not looked at).  out: n results; out_exons, out_steps: cap entries; *n_out: exons written, never more
+ * than 2 * n_exons_total.  One upload, one download; synchronous and batched like the other pgpu_index_* queries.
+ *  - PGPU_EINVAL for the whole call only for structure: what pgpu_index_factorizations lists, orig_off + est_len >
+ *    ests_len, and small_params == NULL (no message) or small_params->reserved != 0.  Whatever concerns the VALUES of the
+ *    exons is HOST for that query, exactly as in the plan form.
+ *  - PGPU_ENOSPC, with the needed count in *n_out and nothing written to out, out_exons or out_steps, when cap is too small.
+ *  - n == 0 is PGPU_OK (*n_out = 0).  idx may be built or loaded; the classification tables are built on first use as for
+ *    pgpu_index_small_exons. */
+int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                    const pgpu_factor* exons, size_t n_exons_total, const pgpu_final_query* q, size_t n,
+                                    const pgpu_fact_params* params, const pgpu_small_params* small_params,
+                                    pgpu_final_result* out, pgpu_factor* out_exons, uint8_t* out_steps, size_t cap, size_t* n_out);
+/* HIP-event time of the whole device part (both drivers) of the calling thread's last pgpu_index_final_factorizations on
+ * a context with timing on (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_final_factorizations_kernel_ms(void);
 
 /* page-locked host memory for the buffers handed to the fetch calls (a pageable destination
  * makes the runtime stage the copy); plain malloc'ed memory works too, slower */

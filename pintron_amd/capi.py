@@ -146,6 +146,17 @@ class FactResult(C.Structure):     # pgpu_fact_result
 
 FactQuery = GapsQuery              # pgpu_fact_query: n_exons == 0 is "no candidate"
 
+
+class FinalResult(C.Structure):    # pgpu_final_result
+    _fields_ = [("outcome", C.c_uint8), ("stage", C.c_uint8), ("detail", C.c_uint16), ("first_exon", C.c_uint32),
+                ("n_exons", C.c_uint16), ("n_merged", C.c_uint16), ("total_edit", C.c_uint32), ("tail_added", C.c_uint32),
+                ("polyA", C.c_uint8), ("polyadenil", C.c_uint8), ("recovered", C.c_uint8), ("refused", C.c_uint8),
+                ("n_removed", C.c_uint16), ("n_added", C.c_uint16), ("n_cleaned", C.c_uint16), ("prefix_added", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+FinalQuery = TailQuery             # pgpu_final_query: n_exons == 0 is "no candidate"
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -189,6 +200,11 @@ FACT_PARAMS_DTYPE = [("complexity_threshold", "<f8"), ("suffpref_length_on_est",
 FACT_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("first_exon", "<u4"), ("n_exons", "<u2"),
                      ("n_merged", "<u2"), ("total_edit", "<u4")]
 FACT_QUERY_DTYPE = GAPS_QUERY_DTYPE
+FINAL_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("first_exon", "<u4"), ("n_exons", "<u2"),
+                      ("n_merged", "<u2"), ("total_edit", "<u4"), ("tail_added", "<u4"), ("polyA", "u1"), ("polyadenil", "u1"),
+                      ("recovered", "u1"), ("refused", "u1"), ("n_removed", "<u2"), ("n_added", "<u2"), ("n_cleaned", "<u2"),
+                      ("prefix_added", "u1"), ("reserved", "u1")]
+FINAL_QUERY_DTYPE = TAIL_QUERY_DTYPE
 
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
@@ -206,6 +222,7 @@ assert C.sizeof(TailQuery) == 32 and C.sizeof(TailResult) == 16
 assert C.sizeof(SmallParams) == 8 and C.sizeof(SmallResult) == 24
 assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
 assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
+assert C.sizeof(FinalResult) == 32 and C.sizeof(FinalQuery) == 32
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -228,6 +245,9 @@ EXPORTS = [
     "pgpu_pairing_plan_candidates_ms", "pgpu_index_candidates", "pgpu_index_candidates_kernel_ms",
     "pgpu_pairing_plan_run_factorizations", "pgpu_pairing_plan_factorization_exons", "pgpu_pairing_plan_fetch_factorizations",
     "pgpu_pairing_plan_factorizations_ms", "pgpu_index_factorizations", "pgpu_index_factorizations_kernel_ms",
+    "pgpu_pairing_plan_create_with_originals", "pgpu_pairing_plan_run_final_factorizations", "pgpu_pairing_plan_final_exons",
+    "pgpu_pairing_plan_fetch_final_factorizations", "pgpu_pairing_plan_final_ms", "pgpu_index_final_factorizations",
+    "pgpu_index_final_factorizations_kernel_ms",
     "pgpu_comm_unique_id", "pgpu_comm_init", "pgpu_gather", "pgpu_allgather", "pgpu_comm_destroy",
     "pgpu_range_push", "pgpu_range_pop", "pgpu_build_info",
     "pgpu_dp_plan_create", "pgpu_dp_plan_create_parts", "pgpu_dp_plan_launch", "pgpu_dp_plan_sync",
@@ -332,6 +352,20 @@ def lib():
                                                 C.POINTER(C.c_uint8), sz, C.POINTER(sz)]
         L.pgpu_index_factorizations_kernel_ms.argtypes = []
         L.pgpu_index_factorizations_kernel_ms.restype = C.c_double
+        L.pgpu_pairing_plan_create_with_originals.argtypes = [vp, vp, C.c_char_p, C.POINTER(u64), sz, C.c_int,
+                                                              C.POINTER(C.c_uint32), C.POINTER(u64), C.c_char_p, sz, C.POINTER(vp)]
+        L.pgpu_pairing_plan_run_final_factorizations.argtypes = [vp, vp, C.POINTER(SmallParams)]
+        L.pgpu_pairing_plan_final_exons.argtypes = [vp]
+        L.pgpu_pairing_plan_final_exons.restype = u64
+        L.pgpu_pairing_plan_fetch_final_factorizations.argtypes = [vp, vp, C.POINTER(FinalResult), C.POINTER(Factor),
+                                                                   C.POINTER(C.c_uint8), sz]
+        L.pgpu_pairing_plan_final_ms.argtypes = [vp, C.c_int]
+        L.pgpu_pairing_plan_final_ms.restype = C.c_double
+        L.pgpu_index_final_factorizations.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(FinalQuery), sz,
+                                                      C.POINTER(FactParams), C.POINTER(SmallParams), C.POINTER(FinalResult),
+                                                      C.POINTER(Factor), C.POINTER(C.c_uint8), sz, C.POINTER(sz)]
+        L.pgpu_index_final_factorizations_kernel_ms.argtypes = []
+        L.pgpu_index_final_factorizations_kernel_ms.restype = C.c_double
         L.pgpu_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.pgpu_host_free.argtypes = [vp, vp]
         L.pgpu_comm_unique_id.argtypes = [vp, vp]
@@ -702,10 +736,62 @@ class Index:
     def factorizations_kernel_ms(self):
         return self.ctx.L.pgpu_index_factorizations_kernel_ms()
 
+    def final_factorizations_raw(self, ests: bytes, exons, queries, n: int, params, small_params, cap: int):
+        """One pgpu_index_final_factorizations call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+        FINAL_QUERY_DTYPE, `params` a FactParams, `small_params` a SmallParams or None.  Returns (rc, results as a numpy array
+        of FINAL_RESULT_DTYPE, exons and step bytes (cap entries each), n_out)."""
+        import numpy as np
+        res = np.zeros(n, dtype=np.dtype(FINAL_RESULT_DTYPE))
+        out_exons = np.zeros(cap, dtype=np.dtype(FACTOR_DTYPE))
+        out_steps = np.zeros(cap, dtype=np.uint8)
+        total = C.c_size_t(0)
+        rc = self.ctx.L.pgpu_index_final_factorizations(
+            self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)), len(exons),
+            queries.ctypes.data_as(C.POINTER(FinalQuery)), n, C.byref(params),
+            None if small_params is None else C.byref(small_params), res.ctypes.data_as(C.POINTER(FinalResult)),
+            out_exons.ctypes.data_as(C.POINTER(Factor)), out_steps.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(total))
+        return rc, res, out_exons, out_steps, total.value
+
+    def final_factorizations(self, ests: bytes, exons, queries, complexity_threshold=20.0, suffpref_length_on_est=30,
+                             suffpref_length_for_intron=70, suffpref_length_on_gen=30, min_intron_length=40):
+        """Every candidate `queries` names through clean, gaps, refine, tail and small in one call (n_exons == 0: no
+        candidate): (results as a numpy array of FINAL_RESULT_DTYPE, the final exons, compact, and their step bytes)."""
+        prm = FactParams(complexity_threshold, suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen,
+                         min_intron_length)
+        rc, res, out_exons, out_steps, total = self.final_factorizations_raw(ests, exons, queries, len(queries), prm,
+                                                                             SmallParams(min_intron_length, 0), 2 * len(exons))
+        self.ctx.check(rc)
+        return res, out_exons[:total], out_steps[:total]
+
+    def final_factorizations_kernel_ms(self):
+        return self.ctx.L.pgpu_index_final_factorizations_kernel_ms()
+
     def close(self):
         if self.h:
             self.ctx.L.pgpu_index_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
+
+
+def final_handoffs_probe(ctx, tlen, ests_len, q, fres, fex, tres, tex, tst, sres, sex, sst):
+    """pgpu_final_handoffs_probe (pintron_amd/csrc/pgpu_final.hip; no part of the C-ABI's header): the three hand-off kernels
+    of the final stage over stage results the caller made, numpy arrays in the layouts of the driver's block.  Returns (rc,
+    tail queries, small queries, small's input exons, results, exons, steps)."""
+    import numpy as np
+    n, E = len(q), len(fex)
+    tq = np.zeros(n, dtype=np.dtype(TAIL_QUERY_DTYPE))
+    sq = np.zeros(n, dtype=np.dtype(SMALL_QUERY_DTYPE))
+    ex_sin = np.zeros(E + n, dtype=np.dtype(FACTOR_DTYPE))
+    res = np.zeros(n, dtype=np.dtype(FINAL_RESULT_DTYPE))
+    out_exons = np.zeros(2 * E, dtype=np.dtype(FACTOR_DTYPE))
+    out_steps = np.zeros(2 * E, dtype=np.uint8)
+    total = C.c_size_t(0)
+    f = ctx.L.pgpu_final_handoffs_probe
+    f.argtypes = [C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 12 + \
+        [C.POINTER(C.c_size_t)]
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = f(ctx.h, tlen, ests_len, p(q), n, p(fres), p(fex), E, p(tres), p(tex), p(tst), p(sres), p(sex), p(sst), p(tq), p(sq), p(ex_sin),
+           p(res), p(out_exons), p(out_steps), C.byref(total))
+    return rc, tq, sq, ex_sin, res, out_exons[:total.value], out_steps[:total.value]
 
 
 class MegParams(C.Structure):       # pgpu_meg_params; defaults = src/options.ggo:94-370
@@ -737,18 +823,39 @@ class PairingPlan:
     run_meg()/fetch_meg() = the MEG stage behind the pairings."""
     STAGES = ["locate", "chain", "count+scan", "fill", "cross+scan", "emit"]
 
-    def __init__(self, ctx: Context, index: Index, patterns, resident=False):
+    def __init__(self, ctx: Context, index: Index, patterns, resident=False, originals=None):
+        """originals: {pattern index: the ORIGINAL sequence of that pattern (the pattern is the working one)}, for the
+        patterns where the two differ; only the final stage reads them"""
         import numpy as np
         self.ctx, self.n_pat = ctx, len(patterns)
         self._blob = b"".join(patterns)
         self._off = np.zeros(len(patterns) + 1, dtype=np.uint64)
         np.cumsum([len(p) for p in patterns], out=self._off[1:])
         self.h = C.c_void_p()
+        if originals is not None:
+            which = sorted(originals)
+            rc = self.create_with_originals_raw(ctx, index, self._blob, self._off, self.n_pat, resident,
+                                                np.array(which, dtype=np.uint32), [originals[k] for k in which], self.h)
+            ctx.check(rc)
+            return
         # resident: the buffers a run writes are shared with the context's other resident plans (results valid
         # until another of them runs)
         create = ctx.L.pgpu_pairing_plan_create_resident if resident else ctx.L.pgpu_pairing_plan_create
         ctx.check(create(ctx.h, index.h, self._blob, self._off.ctypes.data_as(C.POINTER(C.c_uint64)),
                          self.n_pat, C.byref(self.h)))
+
+    @staticmethod
+    def create_with_originals_raw(ctx, index, blob, off, n_pat, resident, orig_pat, orig_seqs, handle, null_lists=False):
+        """One pgpu_pairing_plan_create_with_originals call as it is: orig_pat a numpy uint32 array, orig_seqs the
+        sequences it names.  Returns rc; `handle` (a c_void_p) receives the plan."""
+        import numpy as np
+        first = np.zeros(len(orig_seqs) + 1, dtype=np.uint64)
+        np.cumsum([len(s) for s in orig_seqs], out=first[1:])
+        return ctx.L.pgpu_pairing_plan_create_with_originals(
+            ctx.h, index.h, blob, off.ctypes.data_as(C.POINTER(C.c_uint64)), n_pat, int(resident),
+            None if null_lists else orig_pat.ctypes.data_as(C.POINTER(C.c_uint32)),
+            None if null_lists else first.ctypes.data_as(C.POINTER(C.c_uint64)), b"".join(orig_seqs), len(orig_seqs),
+            C.byref(handle))
 
     def run(self, min_factor_len=15, rate=0.2):
         prm = PairingParams(min_factor_len, 0, rate)
@@ -831,6 +938,37 @@ class PairingPlan:
     def factorizations_ms(self, k=0):
         """HIP-event time of the last run_factorizations: k = 0 the whole call, 1 clean, 2 gaps, 3 refine"""
         return self.ctx.L.pgpu_pairing_plan_factorizations_ms(self.h, k)
+
+    def run_final_factorizations_raw(self, min_intron_length=40, reserved=0, no_params=False):
+        prm = SmallParams(min_intron_length, reserved)
+        return self.ctx.L.pgpu_pairing_plan_run_final_factorizations(self.ctx.h, self.h, None if no_params else C.byref(prm))
+
+    def run_final_factorizations(self, min_intron_length=40):
+        """every factorization of the last run_factorizations through tail and small, where it lies; returns the number of
+        exons of the answer"""
+        self.ctx.check(self.run_final_factorizations_raw(min_intron_length))
+        return self.ctx.L.pgpu_pairing_plan_final_exons(self.h)
+
+    def fetch_final_factorizations_raw(self, cap=None):
+        """(rc, results as a numpy array of FINAL_RESULT_DTYPE, one per pattern; the final exons, compact; their step bytes)"""
+        import numpy as np
+        n = self.ctx.L.pgpu_pairing_plan_final_exons(self.h) if cap is None else cap
+        res = np.zeros(self.n_pat, dtype=np.dtype(FINAL_RESULT_DTYPE))
+        exons = np.zeros(n, dtype=np.dtype(FACTOR_DTYPE))
+        steps = np.zeros(n, dtype=np.uint8)
+        rc = self.ctx.L.pgpu_pairing_plan_fetch_final_factorizations(
+            self.ctx.h, self.h, res.ctypes.data_as(C.POINTER(FinalResult)), exons.ctypes.data_as(C.POINTER(Factor)),
+            steps.ctypes.data_as(C.POINTER(C.c_uint8)), n)
+        return rc, res, exons, steps
+
+    def fetch_final_factorizations(self):
+        rc, res, exons, steps = self.fetch_final_factorizations_raw()
+        self.ctx.check(rc)
+        return res, exons, steps
+
+    def final_ms(self, k=0):
+        """HIP-event time of the last run_final_factorizations: k = 0 the whole call, 1 tail, 2 small"""
+        return self.ctx.L.pgpu_pairing_plan_final_ms(self.h, k)
 
     def close(self):
         if self.h:

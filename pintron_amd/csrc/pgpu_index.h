@@ -83,6 +83,7 @@ enum PlanSlot : int {
   SLOT_PCODE, SLOT_PBAD,
   SLOT_CAND_RES, SLOT_CAND_CNT, SLOT_CAND_FIRST, SLOT_CAND_EXONS,
   SLOT_FACT, SLOT_FACT_WS,
+  SLOT_ORIG_OFF, SLOT_FINAL,
   PLAN_SLOTS
 };
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool);
@@ -138,6 +139,31 @@ struct pgpu_fact_job {
   unsigned long long total; uint32_t undersized;
 };
 hipError_t pgpu_fact_drive(pgpu_ctx* ctx, pgpu_fact_job& job, const pgpu_fact_params& prm);
+// pgpu_final.hip: the answer of pgpu_fact_drive, where it lies (`fact_block`, the block of a job of the same n and
+// n_exons_total, read only), through the tail and the small stage.  The ESTs are either the queries of the index form (fq) or
+// a plan's pattern offsets and its table of original offsets (pat_off, orig_off; fq null); `ests_len` bytes lie behind
+// `ests`, originals included.  `block` holds final_layout(n, n_exons_total, pgpu_scan_tmp_bytes(n + 1)).total bytes
+// (pgpu_final.h), where the outcomes (res), the compact exons and their step bytes are found afterwards.  The one host wait
+// of the drive is its last statement: `total` (exons of the answer) is set on return.
+struct ClassView;          // pgpu_classify.h
+struct pgpu_final_job {
+  LcfIndexView ix; const ClassView* cv;
+  const uint8_t* ests; size_t ests_len;
+  const pgpu_final_query* fq;
+  const unsigned long long* pat_off; const unsigned long long* orig_off;
+  const uint8_t* fact_block;
+  uint32_t n, n_exons_total;
+  int min_intron_length;
+  uint8_t* block;
+  hipEvent_t ev[6];            // null without timing: 0-1 the whole drive, 2-3 tail_kernel, 4-5 small_kernel
+  unsigned long long total;
+  // Null in every call of the library.  pgpu_final_handoffs_probe sets both: host arrays in the layout of the block's
+  // tr / ex_tout / tsteps and sr / ex_sout / ssteps that are copied in where the stage kernel would have written them, and
+  // the kernel is not launched -- the hand-off kernels then run over results no input brings through the stages.
+  struct Given { const void* results; const pgpu_factor* exons; const uint8_t* steps; };
+  const Given* given_tail = nullptr; const Given* given_small = nullptr;
+};
+hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& job);
 // PGPU_TRACE_ALLOC=1: every page-locked host allocation of the library on stderr (size, address, call site)
 #include <cstdio>
 #include <cstdlib>

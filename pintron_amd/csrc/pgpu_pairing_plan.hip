@@ -20,6 +20,9 @@
 
 #include "pgpu_index.h"
 #include "pgpu_fact.h"
+#include "pgpu_final.h"
+#include "pgpu_small.h"
+#include "pgpu_classify.h"
 
 namespace {
 
@@ -364,14 +367,15 @@ void pair_emit_kernel(const unsigned long long* __restrict__ pat_off,
 // compare one), and raises the plan to k when it succeeds.  A fetch of stage k asks for stage k.  A plan without
 // patterns has nothing to compute: its runs succeed without their predecessor (run_factorizations still asks for
 // run_candidates), and fetch and fetch_meg answer whatever ran.
-enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS };
+enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS };
 
 // the plan's events (made only when the context times its calls): seven around the six pairing stages, a pair each for
-// the MEG and the candidate stage, the eight of pgpu_fact_job
-enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, N_EVENTS = 19 };
+// the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job
+enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, N_EVENTS = 25 };
 
 struct pgpu_pairing_plan {
   pgpu_ctx* owner = nullptr;
+  const pgpu_index* idx = nullptr;                     // for the views the small stage takes (pgpu_index_lcf_view, pgpu_class_view_get)
   PairIndexView ix{};
   size_t n_pat = 0;
   unsigned long long total_pos = 0;
@@ -385,6 +389,10 @@ struct pgpu_pairing_plan {
   uint8_t* d_pats = nullptr;
   unsigned long long* d_pat_off = nullptr;
   uint32_t *d_pcode = nullptr, *d_pbad = nullptr;     // the patterns at 2 bits per base + flag bits (PackedSeq)
+  // the original sequences of the patterns that have one, behind the pattern bytes in d_pats: one offset per pattern
+  // (d_pat_off itself in a plan without originals), and the bytes that lie behind d_pats in all
+  unsigned long long* d_orig_off = nullptr;
+  size_t seq_bytes = 0;
   hipEvent_t ev[N_EVENTS] = {nullptr};
   // pairings
   uint32_t *d_lo = nullptr, *d_hi = nullptr, *d_a = nullptr, *d_thr = nullptr, *d_cnt = nullptr,
@@ -419,6 +427,11 @@ struct pgpu_pairing_plan {
   size_t fact_cap = 0, fact_ws_cap = 0;
   unsigned long long fact_total = 0;
   float fact_ms[4] = {0};
+  // final stage (pgpu_final.hip) over the factorizations of the last run_factorizations
+  uint8_t* d_final = nullptr;
+  size_t final_cap = 0;
+  unsigned long long final_total = 0;
+  float final_ms[3] = {0};
 };
 
 static void lower(pgpu_pairing_plan* p, Stage s) { if (p->stage > s) p->stage = s; }
@@ -519,24 +532,28 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_keep); hipFree(p->d_out); hipFree(p->d_tmp);
     hipFree(p->d_meg_scratch); hipFree(p->d_meg_info); hipFree(p->d_meg_bytes); hipFree(p->d_meg_off); hipFree(p->d_meg_out);
     hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
-    hipFree(p->d_fact); hipFree(p->d_fact_ws);
+    hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final);
+    if (p->d_orig_off != p->d_pat_off) hipFree(p->d_orig_off);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
   delete p;
 }
 
 static int pairing_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const char* patterns,
-                               const uint64_t* pat_off, size_t n_pat, bool resident, pgpu_pairing_plan** out) {
+                               const uint64_t* pat_off, size_t n_pat, bool resident, const uint32_t* orig_pat,
+                               const uint64_t* orig_first, const char* orig_bytes, size_t n_orig, pgpu_pairing_plan** out) {
   if (!ctx || !idx || !out || !pat_off || (n_pat && pat_off[n_pat] && !patterns)) return PGPU_EINVAL;
   *out = nullptr;
   for (size_t i = 0; i < n_pat; ++i)
     if (pat_off[i + 1] < pat_off[i] || pat_off[i + 1] - pat_off[i] > 0x7fffffffull) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad pattern offsets");
+  if (const char* wrong = originals_wrong(pat_off, n_pat, orig_pat, orig_first, orig_bytes, n_orig)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, wrong);
+  const size_t orig_total = n_orig ? (size_t)(orig_first[n_orig] - orig_first[0]) : 0;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   std::unique_ptr<pgpu_pairing_plan, void (*)(pgpu_pairing_plan*)> hold(new (std::nothrow) pgpu_pairing_plan(), pairing_plan_free);
   pgpu_pairing_plan* p = hold.get();
   if (!p) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "out of host memory");
   hipStream_t st = pgpu_ctx_stream(ctx);
-  p->owner = ctx; p->ix = pgpu_index_pair_view(idx);
+  p->owner = ctx; p->idx = idx; p->ix = pgpu_index_pair_view(idx);
   p->n_pat = n_pat; p->total_pos = n_pat ? pat_off[n_pat] : 0;
   const size_t tp = (size_t)p->total_pos, bad_words = (tp + 31) / 32;
   p->resident = resident && pgpu_ctx_pool_share(ctx, PLAN_POOL);
@@ -544,16 +561,20 @@ static int pairing_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const char*
   p->tmp_bytes = pgpu_scan_tmp_bytes(std::max(tp, n_pat) + 1);
   if (p->resident) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_off = up(tp + 64), o_code = o_off + up((n_pat + 1) * sizeof(unsigned long long)),
-                 o_bad = o_code + up((2 * bad_words + 4) * sizeof(uint32_t)), total = o_bad + up((bad_words + 4) * sizeof(uint32_t));
+    const size_t o_off = up(tp + orig_total + 64), o_code = o_off + up((n_pat + 1) * sizeof(unsigned long long)),
+                 o_bad = o_code + up((2 * bad_words + 4) * sizeof(uint32_t)), o_orig = o_bad + up((bad_words + 4) * sizeof(uint32_t)),
+                 total = o_orig + (n_orig ? up(n_pat * sizeof(unsigned long long)) : 0);
     PLAN_TRY(hipMalloc(&p->d_resident, total));
     pgpu_trace_alloc("resident plan", p->d_resident, total);
     uint8_t* base = (uint8_t*)p->d_resident;
     p->d_pats = base; p->d_pat_off = (unsigned long long*)(base + o_off);
     p->d_pcode = (uint32_t*)(base + o_code); p->d_pbad = (uint32_t*)(base + o_bad);
+    p->d_orig_off = n_orig ? (unsigned long long*)(base + o_orig) : p->d_pat_off;
   } else {
-    PLAN_NEED(p->d_pats = plan_alloc<uint8_t>(p, SLOT_PATS, tp + 64));
+    PLAN_NEED(p->d_pats = plan_alloc<uint8_t>(p, SLOT_PATS, tp + orig_total + 64));
     PLAN_NEED(p->d_pat_off = plan_alloc<unsigned long long>(p, SLOT_PAT_OFF, n_pat + 1));
+    p->d_orig_off = p->d_pat_off;
+    if (n_orig) PLAN_NEED(p->d_orig_off = plan_alloc<unsigned long long>(p, SLOT_ORIG_OFF, n_pat));
     PLAN_NEED(run_buffers(p));
     PLAN_NEED(p->d_pcode = plan_alloc<uint32_t>(p, SLOT_PCODE, 2 * bad_words + 4));
     PLAN_NEED(p->d_pbad = plan_alloc<uint32_t>(p, SLOT_PBAD, bad_words + 4));
@@ -561,6 +582,17 @@ static int pairing_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const char*
   PLAN_TRY(plan_events(p, EV_PAIRS, EV_MEG - EV_PAIRS));
   if (tp) PLAN_TRY(hipMemcpyAsync(p->d_pats, patterns, tp, hipMemcpyHostToDevice, st));
   PLAN_TRY(hipMemcpyAsync(p->d_pat_off, pat_off, (n_pat + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  p->seq_bytes = tp + orig_total;
+  std::unique_ptr<unsigned long long[]> table;         // alive until the copy has been waited for
+  if (n_orig) {
+    // the table of original offsets: a pattern's own offset, or where its original lies behind the patterns
+    table.reset(new (std::nothrow) unsigned long long[n_pat]);
+    if (!table) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "out of host memory");
+    for (size_t i = 0; i < n_pat; ++i) table[i] = pat_off[i];
+    for (size_t k = 0; k < n_orig; ++k) table[orig_pat[k]] = tp + (orig_first[k] - orig_first[0]);
+    PLAN_TRY(hipMemcpyAsync(p->d_orig_off, table.get(), n_pat * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (orig_total) PLAN_TRY(hipMemcpyAsync(p->d_pats + tp, orig_bytes + orig_first[0], orig_total, hipMemcpyHostToDevice, st));
+  }
   PLAN_TRY(pack_sequence(p->d_pats, tp, p->d_pcode, p->d_pbad, st));
   PLAN_TRY(hipStreamSynchronize(st));
   *out = hold.release();
@@ -569,11 +601,17 @@ static int pairing_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const char*
 
 extern "C" int pgpu_pairing_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const char* patterns,
                                         const uint64_t* pat_off, size_t n_pat, pgpu_pairing_plan** out) {
-  return pairing_plan_create(ctx, idx, patterns, pat_off, n_pat, false, out);
+  return pairing_plan_create(ctx, idx, patterns, pat_off, n_pat, false, nullptr, nullptr, nullptr, 0, out);
 }
 extern "C" int pgpu_pairing_plan_create_resident(pgpu_ctx* ctx, const pgpu_index* idx, const char* patterns,
                                                  const uint64_t* pat_off, size_t n_pat, pgpu_pairing_plan** out) {
-  return pairing_plan_create(ctx, idx, patterns, pat_off, n_pat, true, out);
+  return pairing_plan_create(ctx, idx, patterns, pat_off, n_pat, true, nullptr, nullptr, nullptr, 0, out);
+}
+extern "C" int pgpu_pairing_plan_create_with_originals(pgpu_ctx* ctx, const pgpu_index* idx, const char* patterns,
+                                                       const uint64_t* pat_off, size_t n_pat, int resident, const uint32_t* orig_pat,
+                                                       const uint64_t* orig_first, const char* orig_bytes, size_t n_orig,
+                                                       pgpu_pairing_plan** out) {
+  return pairing_plan_create(ctx, idx, patterns, pat_off, n_pat, resident != 0, orig_pat, orig_first, orig_bytes, n_orig, out);
 }
 
 extern "C" int pgpu_pairing_plan_destroy(pgpu_ctx* ctx, pgpu_pairing_plan* p) {
@@ -814,6 +852,65 @@ extern "C" int pgpu_pairing_plan_fetch_factorizations(pgpu_ctx* ctx, pgpu_pairin
   if (p->fact_total) {
     PLAN_TRY(hipMemcpyAsync(exons, p->d_fact + L.out_exons, (size_t)p->fact_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
     PLAN_TRY(hipMemcpyAsync(steps, p->d_fact + L.out_steps, (size_t)p->fact_total, hipMemcpyDeviceToHost, st));
+  }
+  PLAN_TRY(pgpu_ctx_wait(ctx));
+  return PGPU_OK;
+}
+
+// ---- the factorizations of the last run_factorizations through tail and small, where they lie (pgpu_final.hip) --------
+extern "C" int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_small_params* prm) {
+  if (!ctx || !p || !prm) return PGPU_EINVAL;
+  p->final_total = 0;
+  for (auto& m : p->final_ms) m = 0.f;
+  lower(p, FACTORIZATIONS);
+  if (!small_params_ok(prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad small-chains parameters (reserved != 0)");
+  if (p->stage < FACTORIZATIONS)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_final_factorizations needs the factorizations of pgpu_pairing_plan_run_factorizations");
+  if (p->n_pat == 0) return reached(p, FINALS);
+  if (const int rc = still_owns(ctx, p, "factorizations")) return rc;
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  ClassView cv;
+  if (const int rc = pgpu_class_view_get(ctx, p->idx, &cv)) return rc;
+  if (p->resident) p->d_final = nullptr;                                       // taken anew: the pool may have moved
+  const ProfRange range("final factorizations");
+  const FinalLayout L = final_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
+  PLAN_NEED(p->d_final = plan_grow(p, p->d_final, &p->final_cap, L.total, L.total / 8, SLOT_FINAL));
+  PLAN_TRY(plan_events(p, EV_FINAL, 6));
+  pgpu_final_job job;
+  job.ix = pgpu_index_lcf_view(p->idx);
+  if (!job.ix.focc || !job.ix.rmq) job.ix.first_bad = 0;      // as pgpu_index_small_chains: every prefix question is refused = 3
+  job.cv = &cv;
+  job.ests = p->d_pats; job.ests_len = p->seq_bytes;
+  job.fq = nullptr; job.pat_off = p->d_pat_off; job.orig_off = p->d_orig_off;
+  job.fact_block = p->d_fact;
+  job.n = (uint32_t)p->n_pat; job.n_exons_total = (uint32_t)p->cand_total;
+  job.min_intron_length = prm->min_intron_length;
+  job.block = p->d_final;
+  for (int k = 0; k < 6; ++k) job.ev[k] = p->ev[EV_FINAL + k];
+  PLAN_TRY(pgpu_final_drive(ctx, job));
+  p->final_total = job.total;
+  if (p->ev[EV_FINAL]) for (int k = 0; k < 3; ++k) hipEventElapsedTime(&p->final_ms[k], p->ev[EV_FINAL + 2 * k], p->ev[EV_FINAL + 2 * k + 1]);
+  return reached(p, FINALS);
+}
+
+extern "C" uint64_t pgpu_pairing_plan_final_exons(const pgpu_pairing_plan* p) { return p ? p->final_total : 0; }
+extern "C" double pgpu_pairing_plan_final_ms(const pgpu_pairing_plan* p, int k) { return (p && k >= 0 && k < 3) ? p->final_ms[k] : 0.0; }
+
+extern "C" int pgpu_pairing_plan_fetch_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_final_result* out,
+                                                            pgpu_factor* exons, uint8_t* steps, size_t cap) {
+  if (!ctx || !p || (p->n_pat && !out) || (cap && (!exons || !steps))) return PGPU_EINVAL;
+  if (p->stage < FINALS)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_final_factorizations needs pgpu_pairing_plan_run_final_factorizations first");
+  if (const int rc = still_owns(ctx, p, "results")) return rc;
+  if (cap < p->final_total) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_pat == 0) return PGPU_OK;
+  const FinalLayout L = final_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
+  PLAN_TRY(hipMemcpyAsync(out, p->d_final + L.res, p->n_pat * sizeof(pgpu_final_result), hipMemcpyDeviceToHost, st));
+  if (p->final_total) {
+    PLAN_TRY(hipMemcpyAsync(exons, p->d_final + L.out_exons, (size_t)p->final_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
+    PLAN_TRY(hipMemcpyAsync(steps, p->d_final + L.out_steps, (size_t)p->final_total, hipMemcpyDeviceToHost, st));
   }
   PLAN_TRY(pgpu_ctx_wait(ctx));
   return PGPU_OK;

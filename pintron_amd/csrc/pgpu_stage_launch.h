@@ -1,7 +1,7 @@
 // The chained stage kernels (clean_kernel, gaps_kernel, chain_kernel, tail_kernel, small_kernel) as plain launches over device pointers,
-// for a caller that has the ESTs, the exons and the queries in HBM already: the factorization driver of pgpu_fact.hip (which
-// does not append the tail and small stages yet).  Each of pgpu_clean.hip, pgpu_gaps.hip, pgpu_chain.hip, pgpu_tail.hip and
-// pgpu_small.hip launches its
+// for a caller that has the ESTs, the exons and the queries in HBM already: the factorization driver of pgpu_fact.hip (clean,
+// gaps, refine) and the final driver of pgpu_final.hip behind it (tail, small).  Each of pgpu_clean.hip, pgpu_gaps.hip,
+// pgpu_chain.hip, pgpu_tail.hip and pgpu_small.hip launches its
 // kernel through the function below from its public entry too, so there is one launch per kernel.  Beside them the one rule of a public entry that the driver has to repeat on
 // the device: what an end exon of a clean query asks of the per-wave workspace (clean_query_need), __host__ __device__ so
 // that the entry's validator and the driver's hand-off kernel run the same code.
