@@ -997,6 +997,97 @@ int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const 
  * a context with timing on (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_final_factorizations_kernel_ms(void);
 
+/* ------------------------------------------------------------------------------------------ */
+/* units -- from the finals of the patterns to est-fact's answer per INPUT EST: a unit is an   */
+/* input EST with its reverse-complement sibling (src/main-est-fact.c:249-291: the forward      */
+/* strand first, the sibling only when the forward one has no factorization).  Per unit one     */
+/* verdict, and for an ALIGNED unit the exact bytes of the group est-fact writes into its packed */
+/* records (include/pintron_records.h; pintron_amd/host/ef_estfact.c:                            */
+/* ef_write_factorization_records, the selection rules of src/io-multifasta.c:187-241), after    */
+/* remove_factorizations_with_very_small_exons (src/factorization-refinement.c:84-111).  A caller */
+/* of the chain copies bytes for every settled unit and runs its own path for the HOST ones.     */
+/* Nothing in the library calls these entries yet.                                              */
+/* ------------------------------------------------------------------------------------------ */
+#define PGPU_UNIT_NO_SIBLING 0xffffffffu
+#define PGPU_UNIT_FWD_SUFF_POLYA 1u   /* info->suff_polyA_length != -1 of the forward sequence */
+#define PGPU_UNIT_REV_SUFF_POLYA 2u   /* ... of the sibling as prepared (ef_copy_and_reverse)   */
+typedef struct {
+  uint32_t est_index;       /* position of the EST in ests.txt: copied into the group, any value */
+  uint32_t fwd, rev;        /* pattern indices; rev == PGPU_UNIT_NO_SIBLING: a fixed-strand EST */
+  uint32_t flags;           /* PGPU_UNIT_*_SUFF_POLYA */
+} pgpu_unit_query;          /* 16 bytes */
+typedef struct {
+  int32_t pref_N_length;    /* of the genomic sequence (ef_seq.pref_N_length), in [0, 2^30] */
+  uint8_t retain_externals; /* 0 or 1 */
+  uint8_t reserved[3];
+} pgpu_unit_params;         /* 8 bytes */
+#define PGPU_UNIT_HOST      0u   /* the caller runs its own path for this EST */
+#define PGPU_UNIT_UNALIGNED 1u   /* no factorization on either strand: no group, no entry of processed-ests.txt */
+#define PGPU_UNIT_ALIGNED   2u   /* blob[first_byte .. first_byte + n_bytes) is the EST's group */
+typedef struct {
+  uint8_t  verdict, strand;   /* strand: the pattern that decided (0 fwd, 1 rev) */
+  uint8_t  reason;            /* of that pattern: 0 its final outcome as it stands, 1 a very small exon, 2 an empty graph */
+  uint8_t  n_factorizations;  /* ALIGNED: 0 or 1, else 0 */
+  uint32_t pattern;           /* index of the pattern that decided */
+  uint64_t first_byte;        /* ALIGNED only, else 0 */
+  uint32_t n_bytes, reserved; /* n_bytes: ALIGNED only, else 0 */
+} pgpu_unit_result;         /* 24 bytes: 0, 1, 2, 3, 4, 8, 16, 20 */
+
+/*  - Per pattern, from its pgpu_final_result, its exons, and whether its MEG is empty:
+ *      ALIGNED  outcome DONE and every exon has EST_end + 1 - EST_start > 2 (_UB_VERY_SMALL_EXON_LENGTH_; the difference
+ *               in the reference's int arithmetic, computed here in 64 bits);
+ *      NONE     (no factorization) outcome EMPTY at any stage (reason 0); DONE with a very small exon (reason 1: the
+ *               one factorization is removed and the list is empty); or (HOST, stage 0, detail PGPU_CAND_NOT_PATH) with
+ *               an empty graph (reason 2): source and sink without an edge, whose one-vertex embeddings become
+ *               one-factor factorizations that clean_candidates drops (src/est-factorizations.c:2111-2125).  The
+ *               empty-graph bit is looked at in this last case only;
+ *      HOST     everything else (reason 0).
+ *    The caller's budget and max_number_of_factorizations cannot matter: a path's `work` is at most 128 units against a
+ *    budget of at least 10^6, and one factorization never exceeds a limit >= 1 (0 means no limit).
+ *  - Per unit: fwd ALIGNED -> ALIGNED on strand 0, the sibling is never looked at; fwd HOST -> HOST on strand 0; fwd
+ *    NONE: no sibling -> UNALIGNED (strand 0, the forward pattern and its reason); else the sibling decides (strand 1, its
+ *    index and its reason): ALIGNED -> ALIGNED, NONE -> UNALIGNED, HOST -> HOST.
+ *  - The group of an ALIGNED unit: u32 est_index, u32 n_factorizations, then per factorization u8 polya, u8 polyad,
+ *    u16 n_exons and the exons as four i32 each: EST_start + 1, EST_end + 1, pref_N_length + GEN_start + 1,
+ *    pref_N_length + GEN_end + 1, the additions done in uint32_t.  retain_externals != 0: every exon, with the final
+ *    result's polyA and polyadenil.  retain_externals == 0: the factorization is written only when n > 2 || (n == 2 && the
+ *    deciding strand has a polyA suffix); both flags are 0; the first exon is dropped, and the last one unless that strand
+ *    has a polyA suffix; a factorization that is not written leaves a group of 8 bytes with n_factorizations == 0.
+ *  - UNALIGNED and HOST units have no bytes.  The blob is compact and in UNIT order, whatever the pattern order: a call
+ *    whose units are all settled produces est-fact's blob for those ESTs byte for byte.  Every offset is a multiple of 4. */
+
+/* The form without a plan: fetched or hand-made finals, no index.  res: n_pat results; exons: n_exons_total entries, the
+ * ones res[].first_exon index; empty_graph: a byte per pattern (0 or not), or NULL = none is empty; q: n units; out: n
+ * results; blob: blob_cap bytes; *blob_len: bytes written.  One upload, one download; synchronous.
+ *  - PGPU_EINVAL for the whole call, for structure only: a null pointer (no message); fwd >= n_pat; rev >= n_pat and not
+ *    PGPU_UNIT_NO_SIBLING; fwd == rev; a pattern named by two units; flag bits beyond 0-1; reserved != 0;
+ *    retain_externals > 1; pref_N_length outside [0, 2^30]; an outcome above 2; a DONE result with n_exons == 0,
+ *    n_exons > 128 or first_exon + n_exons > n_exons_total; more than 2^31 - 1 units or patterns.
+ *  - PGPU_ENOSPC, with the needed size in *blob_len and nothing written to out or blob, when blob_cap is too small.
+ *  - n == 0 is PGPU_OK (*blob_len = 0). */
+int pgpu_unit_records(pgpu_ctx* ctx, const pgpu_final_result* res, size_t n_pat, const pgpu_factor* exons, size_t n_exons_total,
+                      const uint8_t* empty_graph, const pgpu_unit_query* q, size_t n, const pgpu_unit_params* params,
+                      pgpu_unit_result* out, void* blob, size_t blob_cap, size_t* blob_len);
+/* HIP-event time of the kernels of the calling thread's last pgpu_unit_records on a context with timing on (as
+ * pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_unit_records_kernel_ms(void);
+
+/* Plan form: the finals of the last pgpu_pairing_plan_run_final_factorizations, where they lie, and the empty-graph bit
+ * from each pattern's MEG record header in HBM (an unflagged record with n_vertices == 2 and n_edges == 0).  The sixth
+ * stage of a plan: the finals stay fetchable and unchanged; a run of any earlier stage takes the units with it.
+ * PGPU_EINVAL (with a message): what the form above refuses in q and params; no run_final_factorizations since the last
+ * run of an earlier stage; the results of a resident plan were overwritten by the run of another one; fetch before the
+ * run.  A null pointer is a bare PGPU_EINVAL (q may be null when n_units == 0).  An empty plan is PGPU_OK.  A rerun gives
+ * the same bytes.  The buffers come from where the MEG stage's do, in a slot of the stage's own.  The one host wait of
+ * the call is its last statement (8 bytes: the byte total). */
+int pgpu_pairing_plan_run_units(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_unit_query* q, size_t n_units,
+                                const pgpu_unit_params* params);
+uint64_t pgpu_pairing_plan_unit_bytes(const pgpu_pairing_plan* plan);   /* bytes of the blob of the last run_units */
+/* out: as many results as the last run_units had units; blob: at least unit_bytes bytes (PGPU_ENOSPC when cap is smaller) */
+int pgpu_pairing_plan_fetch_units(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_unit_result* out, void* blob, size_t cap);
+/* HIP-event time of the last run_units (count + scan + write); 0 without timing */
+double pgpu_pairing_plan_units_ms(const pgpu_pairing_plan* plan);
+
 /* page-locked host memory for the buffers handed to the fetch calls (a pageable destination
  * makes the runtime stage the copy); plain malloc'ed memory works too, slower */
 int pgpu_host_alloc(pgpu_ctx* ctx, size_t bytes, void** out);

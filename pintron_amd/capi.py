@@ -157,6 +157,20 @@ class FinalResult(C.Structure):    # pgpu_final_result
 
 FinalQuery = TailQuery             # pgpu_final_query: n_exons == 0 is "no candidate"
 
+
+class UnitQuery(C.Structure):      # pgpu_unit_query
+    _fields_ = [("est_index", C.c_uint32), ("fwd", C.c_uint32), ("rev", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class UnitParams(C.Structure):     # pgpu_unit_params
+    _fields_ = [("pref_N_length", C.c_int32), ("retain_externals", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class UnitResult(C.Structure):     # pgpu_unit_result
+    _fields_ = [("verdict", C.c_uint8), ("strand", C.c_uint8), ("reason", C.c_uint8), ("n_factorizations", C.c_uint8),
+                ("pattern", C.c_uint32), ("first_byte", C.c_uint64), ("n_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -205,6 +219,11 @@ FINAL_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("f
                       ("recovered", "u1"), ("refused", "u1"), ("n_removed", "<u2"), ("n_added", "<u2"), ("n_cleaned", "<u2"),
                       ("prefix_added", "u1"), ("reserved", "u1")]
 FINAL_QUERY_DTYPE = TAIL_QUERY_DTYPE
+UNIT_NO_SIBLING, UNIT_FWD_SUFF_POLYA, UNIT_REV_SUFF_POLYA = 0xffffffff, 1, 2
+UNIT_HOST, UNIT_UNALIGNED, UNIT_ALIGNED = range(3)
+UNIT_QUERY_DTYPE = [("est_index", "<u4"), ("fwd", "<u4"), ("rev", "<u4"), ("flags", "<u4")]
+UNIT_RESULT_DTYPE = [("verdict", "u1"), ("strand", "u1"), ("reason", "u1"), ("n_factorizations", "u1"), ("pattern", "<u4"),
+                     ("first_byte", "<u8"), ("n_bytes", "<u4"), ("reserved", "<u4")]
 
 SEXON_MAX_ELEN = 64
 SEXON_QUERY_DTYPE = [("e_off", "<u8"), ("elen", "<u4"), ("allgstart", "<u4"), ("allglen", "<u4"), ("f1slen", "<u4"),
@@ -223,6 +242,7 @@ assert C.sizeof(SmallParams) == 8 and C.sizeof(SmallResult) == 24
 assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
 assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
 assert C.sizeof(FinalResult) == 32 and C.sizeof(FinalQuery) == 32
+assert C.sizeof(UnitQuery) == 16 and C.sizeof(UnitParams) == 8 and C.sizeof(UnitResult) == 24
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -248,6 +268,8 @@ EXPORTS = [
     "pgpu_pairing_plan_create_with_originals", "pgpu_pairing_plan_run_final_factorizations", "pgpu_pairing_plan_final_exons",
     "pgpu_pairing_plan_fetch_final_factorizations", "pgpu_pairing_plan_final_ms", "pgpu_index_final_factorizations",
     "pgpu_index_final_factorizations_kernel_ms",
+    "pgpu_unit_records", "pgpu_unit_records_kernel_ms", "pgpu_pairing_plan_run_units", "pgpu_pairing_plan_unit_bytes",
+    "pgpu_pairing_plan_fetch_units", "pgpu_pairing_plan_units_ms",
     "pgpu_comm_unique_id", "pgpu_comm_init", "pgpu_gather", "pgpu_allgather", "pgpu_comm_destroy",
     "pgpu_range_push", "pgpu_range_pop", "pgpu_build_info",
     "pgpu_dp_plan_create", "pgpu_dp_plan_create_parts", "pgpu_dp_plan_launch", "pgpu_dp_plan_sync",
@@ -366,6 +388,17 @@ def lib():
                                                       C.POINTER(Factor), C.POINTER(C.c_uint8), sz, C.POINTER(sz)]
         L.pgpu_index_final_factorizations_kernel_ms.argtypes = []
         L.pgpu_index_final_factorizations_kernel_ms.restype = C.c_double
+        L.pgpu_unit_records.argtypes = [vp, C.POINTER(FinalResult), sz, C.POINTER(Factor), sz, C.POINTER(C.c_uint8),
+                                        C.POINTER(UnitQuery), sz, C.POINTER(UnitParams), C.POINTER(UnitResult), vp, sz,
+                                        C.POINTER(sz)]
+        L.pgpu_unit_records_kernel_ms.argtypes = []
+        L.pgpu_unit_records_kernel_ms.restype = C.c_double
+        L.pgpu_pairing_plan_run_units.argtypes = [vp, vp, C.POINTER(UnitQuery), sz, C.POINTER(UnitParams)]
+        L.pgpu_pairing_plan_unit_bytes.argtypes = [vp]
+        L.pgpu_pairing_plan_unit_bytes.restype = u64
+        L.pgpu_pairing_plan_fetch_units.argtypes = [vp, vp, C.POINTER(UnitResult), vp, sz]
+        L.pgpu_pairing_plan_units_ms.argtypes = [vp]
+        L.pgpu_pairing_plan_units_ms.restype = C.c_double
         L.pgpu_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.pgpu_host_free.argtypes = [vp, vp]
         L.pgpu_comm_unique_id.argtypes = [vp, vp]
@@ -794,6 +827,37 @@ def final_handoffs_probe(ctx, tlen, ests_len, q, fres, fex, tres, tex, tst, sres
     return rc, tq, sq, ex_sin, res, out_exons[:total.value], out_steps[:total.value]
 
 
+def unit_params(pref_N_length=0, retain_externals=1, reserved=(0, 0, 0)):
+    return UnitParams(pref_N_length, retain_externals, (C.c_uint8 * 3)(*reserved))
+
+
+def unit_records_raw(ctx, res, exons, empty_graph, queries, n, params, blob_cap, n_pat=None):
+    """One pgpu_unit_records call as it is: `res` a numpy array of FINAL_RESULT_DTYPE (one per pattern), `exons` one of
+    FACTOR_DTYPE, `empty_graph` a numpy uint8 array with a byte per pattern or None, `queries` one of UNIT_QUERY_DTYPE,
+    `params` a UnitParams.  Returns (rc, results as a numpy array of UNIT_RESULT_DTYPE, the blob (blob_cap bytes), blob_len)."""
+    import numpy as np
+    out = np.zeros(min(n, len(queries)), dtype=np.dtype(UNIT_RESULT_DTYPE))      # (n beyond the queries: a call to be refused)
+    blob = np.zeros(blob_cap, dtype=np.uint8)
+    total = C.c_size_t(0)
+    rc = ctx.L.pgpu_unit_records(
+        ctx.h, res.ctypes.data_as(C.POINTER(FinalResult)), len(res) if n_pat is None else n_pat,
+        exons.ctypes.data_as(C.POINTER(Factor)), len(exons),
+        None if empty_graph is None else empty_graph.ctypes.data_as(C.POINTER(C.c_uint8)),
+        queries.ctypes.data_as(C.POINTER(UnitQuery)), n, C.byref(params), out.ctypes.data_as(C.POINTER(UnitResult)),
+        blob.ctypes.data_as(C.c_void_p), blob_cap, C.byref(total))
+    return rc, out, blob, total.value
+
+
+def unit_records(ctx, res, exons, empty_graph, queries, pref_N_length=0, retain_externals=True):
+    """The verdict of every unit `queries` names over the finals (res, exons) and the groups of the ALIGNED ones:
+    (results as a numpy array of UNIT_RESULT_DTYPE, the blob as bytes)."""
+    cap = 12 * len(queries) + 16 * int(res["n_exons"][res["outcome"] == FACT_DONE].sum())
+    rc, out, blob, total = unit_records_raw(ctx, res, exons, empty_graph, queries, len(queries),
+                                            unit_params(pref_N_length, int(bool(retain_externals))), cap)
+    ctx.check(rc)
+    return out, blob[:total].tobytes()
+
+
 class MegParams(C.Structure):       # pgpu_meg_params; defaults = src/options.ggo:94-370
     _fields_ = [("min_factor_len", C.c_uint32), ("min_intron_length", C.c_int32), ("max_intron_length", C.c_int32),
                 ("max_pairings_in_MEG", C.c_uint32), ("max_prefix_discarded_rate", C.c_double),
@@ -822,6 +886,7 @@ class PairingPlan:
     """Patterns resident in HBM; run() = all pairing kernels; fetch() -> (triples[n,3], first[n_pat+1]);
     run_meg()/fetch_meg() = the MEG stage behind the pairings."""
     STAGES = ["locate", "chain", "count+scan", "fill", "cross+scan", "emit"]
+    _n_units = 0                    # units of the last run_units
 
     def __init__(self, ctx: Context, index: Index, patterns, resident=False, originals=None):
         """originals: {pattern index: the ORIGINAL sequence of that pattern (the pattern is the working one)}, for the
@@ -969,6 +1034,38 @@ class PairingPlan:
     def final_ms(self, k=0):
         """HIP-event time of the last run_final_factorizations: k = 0 the whole call, 1 tail, 2 small"""
         return self.ctx.L.pgpu_pairing_plan_final_ms(self.h, k)
+
+    def run_units_raw(self, queries, n, params):
+        """queries: a numpy array of UNIT_QUERY_DTYPE (or None), params: a UnitParams (or None)"""
+        return self.ctx.L.pgpu_pairing_plan_run_units(
+            self.ctx.h, self.h, None if queries is None else queries.ctypes.data_as(C.POINTER(UnitQuery)), n,
+            None if params is None else C.byref(params))
+
+    def run_units(self, queries, pref_N_length=0, retain_externals=True):
+        """the finals of the last run_final_factorizations to one verdict per unit and the groups of the ALIGNED ones, where
+        they lie; returns the bytes of the blob"""
+        self._n_units = len(queries)
+        self.ctx.check(self.run_units_raw(queries, len(queries), unit_params(pref_N_length, int(bool(retain_externals)))))
+        return self.ctx.L.pgpu_pairing_plan_unit_bytes(self.h)
+
+    def fetch_units_raw(self, n_units, cap=None):
+        """(rc, results as a numpy array of UNIT_RESULT_DTYPE, one per unit; the blob as a numpy uint8 array)"""
+        import numpy as np
+        n = self.ctx.L.pgpu_pairing_plan_unit_bytes(self.h) if cap is None else cap
+        out = np.zeros(max(n_units, 1), dtype=np.dtype(UNIT_RESULT_DTYPE))
+        blob = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = self.ctx.L.pgpu_pairing_plan_fetch_units(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(UnitResult)),
+                                                      blob.ctypes.data_as(C.c_void_p), n)
+        return rc, out[:n_units], blob[:n]
+
+    def fetch_units(self):
+        rc, out, blob = self.fetch_units_raw(self._n_units)
+        self.ctx.check(rc)
+        return out, blob.tobytes()
+
+    def units_ms(self):
+        """HIP-event time of the last run_units (count + scan + write)"""
+        return self.ctx.L.pgpu_pairing_plan_units_ms(self.h)
 
     def close(self):
         if self.h:

@@ -84,6 +84,7 @@ enum PlanSlot : int {
   SLOT_CAND_RES, SLOT_CAND_CNT, SLOT_CAND_FIRST, SLOT_CAND_EXONS,
   SLOT_FACT, SLOT_FACT_WS,
   SLOT_ORIG_OFF, SLOT_FINAL,
+  SLOT_UNITS,
   PLAN_SLOTS
 };
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool);
@@ -164,6 +165,24 @@ struct pgpu_final_job {
   const Given* given_tail = nullptr; const Given* given_small = nullptr;
 };
 hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& job);
+// pgpu_unit.hip: the finals of the patterns (`res`, `exons`: n_exons_total entries, read only, where they lie) to one verdict
+// per unit and the groups of the ALIGNED ones.  The empty-graph bit of a pattern is either a byte per pattern (`empty`, may
+// be null: no graph is empty) or read from the header of its MEG record (`recs`, `rec_first`; `empty` is then not looked at).
+// `n_done_exons`: the exons of the DONE results in all (the compact array of the final driver: n_exons_total itself).
+// `block` holds unit_layout(n, n_done_exons, pgpu_scan_tmp_bytes(n + 1)).total bytes (pgpu_unit.h) with the n queries
+// already at its `q`; the results (out) and the blob are found there afterwards.  The one host wait of the drive is its
+// last statement: `total` (bytes of the blob) is set on return.
+struct pgpu_unit_job {
+  const pgpu_final_result* res; const pgpu_factor* exons; uint32_t n_exons_total; size_t n_done_exons;
+  const uint8_t* empty;
+  const uint8_t* recs; const unsigned long long* rec_first;
+  pgpu_unit_params params;
+  uint32_t n;
+  uint8_t* block;
+  hipEvent_t ev[2];            // null without timing: around count + scan + write
+  unsigned long long total;
+};
+hipError_t pgpu_unit_drive(pgpu_ctx* ctx, pgpu_unit_job& job);
 // PGPU_TRACE_ALLOC=1: every page-locked host allocation of the library on stderr (size, address, call site)
 #include <cstdio>
 #include <cstdlib>

@@ -21,6 +21,7 @@
 #include "pgpu_index.h"
 #include "pgpu_fact.h"
 #include "pgpu_final.h"
+#include "pgpu_unit.h"
 #include "pgpu_small.h"
 #include "pgpu_classify.h"
 
@@ -365,13 +366,13 @@ void pair_emit_kernel(const unsigned long long* __restrict__ pat_off,
 // a run of stage k first lowers the plan to k - 1 -- its own results and everything made from them are gone, even when
 // the call is then refused --, asks for stage k - 1 (made with the same min_factor_len, where run_meg and run_candidates
 // compare one), and raises the plan to k when it succeeds.  A fetch of stage k asks for stage k.  A plan without
-// patterns has nothing to compute: its runs succeed without their predecessor (run_factorizations still asks for
-// run_candidates), and fetch and fetch_meg answer whatever ran.
-enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS };
+// patterns has nothing to compute: its runs succeed without their predecessor (run_factorizations and the stages above
+// it still ask for theirs), and fetch and fetch_meg answer whatever ran.
+enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS, UNITS };
 
 // the plan's events (made only when the context times its calls): seven around the six pairing stages, a pair each for
-// the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job
-enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, N_EVENTS = 25 };
+// the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job, the pair of pgpu_unit_job
+enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, N_EVENTS = 27 };
 
 struct pgpu_pairing_plan {
   pgpu_ctx* owner = nullptr;
@@ -432,6 +433,11 @@ struct pgpu_pairing_plan {
   size_t final_cap = 0;
   unsigned long long final_total = 0;
   float final_ms[3] = {0};
+  // unit stage (pgpu_unit.hip) over the finals of the last run_final_factorizations and the headers of the records
+  uint8_t* d_unit = nullptr;
+  size_t unit_cap = 0, n_units = 0;
+  unsigned long long unit_total = 0;
+  float unit_ms = 0.f;
 };
 
 static void lower(pgpu_pairing_plan* p, Stage s) { if (p->stage > s) p->stage = s; }
@@ -532,7 +538,7 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_keep); hipFree(p->d_out); hipFree(p->d_tmp);
     hipFree(p->d_meg_scratch); hipFree(p->d_meg_info); hipFree(p->d_meg_bytes); hipFree(p->d_meg_off); hipFree(p->d_meg_out);
     hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
-    hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final);
+    hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final); hipFree(p->d_unit);
     if (p->d_orig_off != p->d_pat_off) hipFree(p->d_orig_off);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
@@ -912,6 +918,62 @@ extern "C" int pgpu_pairing_plan_fetch_final_factorizations(pgpu_ctx* ctx, pgpu_
     PLAN_TRY(hipMemcpyAsync(exons, p->d_final + L.out_exons, (size_t)p->final_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
     PLAN_TRY(hipMemcpyAsync(steps, p->d_final + L.out_steps, (size_t)p->final_total, hipMemcpyDeviceToHost, st));
   }
+  PLAN_TRY(pgpu_ctx_wait(ctx));
+  return PGPU_OK;
+}
+
+// ---- the finals of the last run_final_factorizations to one verdict per unit and est-fact's groups (pgpu_unit.hip) -----
+extern "C" int pgpu_pairing_plan_run_units(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_unit_query* q, size_t n_units,
+                                           const pgpu_unit_params* prm) {
+  if (!ctx || !p || !prm || (n_units && !q)) return PGPU_EINVAL;
+  p->unit_total = 0; p->n_units = 0; p->unit_ms = 0.f;
+  lower(p, FINALS);
+  if (const char* wrong = unit_params_wrong(*prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, wrong);
+  if (n_units > UNIT_MAX_COUNT || p->n_pat > UNIT_MAX_COUNT)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 units or patterns in one call");
+  {
+    const std::unique_ptr<uint8_t, void (*)(void*)> named((uint8_t*)calloc(p->n_pat ? p->n_pat : 1, 1), free);
+    if (!named) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "no memory for the table of the patterns the units name");
+    if (const char* wrong = unit_queries_wrong(q, n_units, p->n_pat, named.get())) return pgpu_ctx_fail(ctx, PGPU_EINVAL, wrong);
+  }
+  if (p->stage < FINALS)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_units needs the finals of pgpu_pairing_plan_run_final_factorizations");
+  if (p->n_pat == 0 || n_units == 0) return reached(p, UNITS);
+  if (const int rc = still_owns(ctx, p, "finals")) return rc;
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  if (p->resident) p->d_unit = nullptr;                                        // taken anew: the pool may have moved
+  const ProfRange range("units");
+  const UnitLayout L = unit_layout(n_units, (size_t)p->final_total, pgpu_scan_tmp_bytes(n_units + 1));
+  PLAN_NEED(p->d_unit = plan_grow(p, p->d_unit, &p->unit_cap, L.total, L.total / 8, SLOT_UNITS));
+  PLAN_TRY(plan_events(p, EV_UNITS, 2));
+  const FinalLayout F = final_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
+  PLAN_TRY(hipMemcpyAsync(p->d_unit + L.q, q, n_units * sizeof *q, hipMemcpyHostToDevice, pgpu_ctx_stream(ctx)));
+  pgpu_unit_job job;
+  job.res = (const pgpu_final_result*)(p->d_final + F.res); job.exons = (const pgpu_factor*)(p->d_final + F.out_exons);
+  job.n_exons_total = (uint32_t)p->final_total; job.n_done_exons = (size_t)p->final_total;
+  job.empty = nullptr; job.recs = p->d_meg_out; job.rec_first = p->d_meg_off;
+  job.params = *prm; job.n = (uint32_t)n_units; job.block = p->d_unit;
+  job.ev[0] = p->ev[EV_UNITS]; job.ev[1] = p->ev[EV_UNITS + 1];
+  PLAN_TRY(pgpu_unit_drive(ctx, job));
+  p->unit_total = job.total; p->n_units = n_units;
+  if (p->ev[EV_UNITS]) hipEventElapsedTime(&p->unit_ms, p->ev[EV_UNITS], p->ev[EV_UNITS + 1]);
+  return reached(p, UNITS);
+}
+
+extern "C" uint64_t pgpu_pairing_plan_unit_bytes(const pgpu_pairing_plan* p) { return p ? p->unit_total : 0; }
+extern "C" double pgpu_pairing_plan_units_ms(const pgpu_pairing_plan* p) { return p ? p->unit_ms : 0.0; }
+
+extern "C" int pgpu_pairing_plan_fetch_units(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_unit_result* out, void* blob, size_t cap) {
+  if (!ctx || !p || (p->n_units && !out) || (cap && !blob)) return PGPU_EINVAL;
+  if (p->stage < UNITS) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_units needs pgpu_pairing_plan_run_units first");
+  if (const int rc = still_owns(ctx, p, "results")) return rc;
+  if (cap < p->unit_total) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "blob too small");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_units == 0) return PGPU_OK;
+  const UnitLayout L = unit_layout(p->n_units, (size_t)p->final_total, pgpu_scan_tmp_bytes(p->n_units + 1));
+  PLAN_TRY(hipMemcpyAsync(out, p->d_unit + L.out, p->n_units * sizeof(pgpu_unit_result), hipMemcpyDeviceToHost, st));
+  if (p->unit_total) PLAN_TRY(hipMemcpyAsync(blob, p->d_unit + L.blob, (size_t)p->unit_total, hipMemcpyDeviceToHost, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   return PGPU_OK;
 }
