@@ -17,6 +17,7 @@
 
 #include "pgpu_internal.h"
 #include "pgpu_query_call.h"
+#include "pgpu_stage_drive.h"
 #include "pgpu_wave_dp.h"
 #include "pgpu_burset.h"
 #include "pgpu_cand.h"
@@ -214,11 +215,12 @@ extern "C" int pgpu_index_candidates(pgpu_ctx* ctx, const pgpu_index* idx, const
   QueryCall call(ctx, "candidates");
   // the one device block: [records | offsets | results | counts (n + 1) | first_exon (n + 1) | scan workspace]; the exons
   // in a second one, sized by the scan
-  const size_t rec_bytes = (size_t)rec_first[n], tmp_bytes = pgpu_scan_tmp_bytes(n + 1);
-  const size_t o_first = up256(rec_bytes + 4), o_res = o_first + up256((n + 1) * sizeof(uint64_t)),
-               o_cnt = o_res + up256(n * sizeof(pgpu_cand_result)), o_off = o_cnt + up256((n + 1) * sizeof(uint32_t)),
-               o_tmp = o_off + up256((n + 1) * sizeof(uint64_t)), total = o_tmp + up256(tmp_bytes);
-  TRY_HIP(hipMalloc((void**)&call.d, total));
+  const size_t rec_bytes = (size_t)rec_first[n];
+  BlockCarver c{up256(rec_bytes + 4)};
+  const size_t o_first = c.take((n + 1) * sizeof(uint64_t)), o_res = c.take(n * sizeof(pgpu_cand_result)),
+               o_cnt = c.take((n + 1) * sizeof(uint32_t)), o_off = c.take((n + 1) * sizeof(uint64_t)),
+               o_tmp = c.take(pgpu_scan_tmp_bytes(n + 1));
+  TRY_HIP(hipMalloc((void**)&call.d, c.at));
   TRY_HIP(call.timing_events(2));
   if (rec_bytes) TRY_HIP(hipMemcpyAsync(call.d, records, rec_bytes, hipMemcpyHostToDevice, call.st));
   TRY_HIP(hipMemcpyAsync(call.d + o_first, rec_first, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
@@ -230,13 +232,10 @@ extern "C" int pgpu_index_candidates(pgpu_ctx* ctx, const pgpu_index* idx, const
   const unsigned long long* const d_first = (const unsigned long long*)(call.d + o_first);
   TRY_HIP(call.record(0));
   pgpu_cand_launch_count(call.d, d_first, (uint32_t)n, T, tlen, params, d_res, d_cnt, call.st);
-  TRY_HIP(hipMemsetAsync(d_cnt + n, 0, sizeof(uint32_t), call.st));
-  pgpu_exclusive_scan_u32(d_cnt, d_off, n + 1, call.d + o_tmp, call.st);
+  TRY_HIP(drive_scan(d_cnt, d_off, n, call.d + o_tmp, call.st));
   TRY_HIP(call.record(1));
   unsigned long long total_exons = 0;
-  TRY_HIP(hipMemcpyAsync(&total_exons, d_off + n, sizeof total_exons, hipMemcpyDeviceToHost, call.st));
-  TRY_HIP(pgpu_ctx_wait(ctx));
-  TRY_HIP(hipGetLastError());
+  TRY_HIP(drive_total(ctx, d_off, n, &total_exons));
   *n_exons = (size_t)total_exons;
   if (total_exons > exons_cap) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
   TRY_HIP(hipMalloc((void**)&call.d2, total_exons ? (size_t)total_exons * sizeof(pgpu_factor) : 16));

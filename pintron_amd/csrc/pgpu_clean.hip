@@ -327,8 +327,7 @@ extern "C" int pgpu_index_clean_chains(pgpu_ctx* ctx, const pgpu_index* idx, con
   TRY_HIP(hipMemcpyAsync(&undersized, d_undersized, sizeof undersized, hipMemcpyDeviceToHost, call.st));
   TRY_HIP(pgpu_ctx_wait(ctx));
   TRY_HIP(hipGetLastError());
-  if (undersized)
-    return pgpu_ctx_fail(ctx, PGPU_EDEVICE, "clean chains: the workspace of a wave was sized too small for an end-exon alignment");
+  if (undersized) return pgpu_clean_undersized(ctx, "clean chains");
   call.elapsed_ms(0, &t_clean_ms);
   return PGPU_OK;
 }

@@ -8,8 +8,11 @@
 #include <stdint.h>
 
 #include "../../include/pintron_gpu.h"
+#include "pgpu_layout.h"
 
 constexpr int32_t FACT_MAX_SUFFPREF = 1 << 24;      // as suffpref_ok of pgpu_query_call.h
+constexpr char FACT_TOO_MANY[] = "more than 2^31 - 1 queries or exons in one call";      // n and n_exons_total are 32 bits wide
+constexpr char FACT_BAD_PARAMS[] ="bad factorization parameters (a suffpref length outside [0, 2^24])";
 
 inline bool fact_params_ok(const pgpu_fact_params& p) {
   const int32_t v[3] = { p.suffpref_length_on_est, p.suffpref_length_for_intron, p.suffpref_length_on_gen };
@@ -44,20 +47,18 @@ struct FactLayout {
   size_t out_exons, out_steps;                               // the compact answer: at most n_exons_total entries
   size_t total;
 };
-inline size_t fact_up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline FactLayout fact_layout(size_t n, size_t n_exons_total, size_t scan_tmp_bytes) {
-  const size_t ne = n_exons_total + n, exb = fact_up256(ne * sizeof(pgpu_factor)), by = fact_up256(ne);
+  const size_t ne = n_exons_total + n, exb = ne * sizeof(pgpu_factor);
   FactLayout L;
-  size_t at = 0;
-  const auto take = [&at](size_t bytes) { const size_t o = at; at += fact_up256(bytes ? bytes : 1); return o; };
-  L.ex_in = take(exb); L.ex_clean = take(exb); L.ex_gaps = take(exb); L.ex_kept = take(exb); L.ex_refined = take(exb);
-  L.marks = take(by); L.gsteps = take(by); L.rsteps = take(by);
-  L.cq = take(n * sizeof(pgpu_clean_query)); L.cr = take(n * sizeof(pgpu_clean_result));
-  L.gq = take(n * sizeof(pgpu_gaps_query)); L.gr = take(n * sizeof(pgpu_gaps_result));
-  L.rq = take(n * sizeof(pgpu_chain_query)); L.rr = take(n * sizeof(pgpu_chain_result));
-  L.res = take(n * sizeof(pgpu_fact_result)); L.need = take(16);
-  L.counts = take((n + 1) * sizeof(uint32_t)); L.first = take((n + 1) * sizeof(uint64_t)); L.scan_tmp = take(scan_tmp_bytes);
-  L.out_exons = take(n_exons_total * sizeof(pgpu_factor)); L.out_steps = take(n_exons_total);
-  L.total = at;
+  BlockCarver c;
+  L.ex_in = c.take(exb); L.ex_clean = c.take(exb); L.ex_gaps = c.take(exb); L.ex_kept = c.take(exb); L.ex_refined = c.take(exb);
+  L.marks = c.take(ne); L.gsteps = c.take(ne); L.rsteps = c.take(ne);
+  L.cq = c.take(n * sizeof(pgpu_clean_query)); L.cr = c.take(n * sizeof(pgpu_clean_result));
+  L.gq = c.take(n * sizeof(pgpu_gaps_query)); L.gr = c.take(n * sizeof(pgpu_gaps_result));
+  L.rq = c.take(n * sizeof(pgpu_chain_query)); L.rr = c.take(n * sizeof(pgpu_chain_result));
+  L.res = c.take(n * sizeof(pgpu_fact_result)); L.need = c.take(16);
+  L.counts = c.take((n + 1) * sizeof(uint32_t)); L.first = c.take((n + 1) * sizeof(uint64_t)); L.scan_tmp = c.take(scan_tmp_bytes);
+  L.out_exons = c.take(n_exons_total * sizeof(pgpu_factor)); L.out_steps = c.take(n_exons_total);
+  L.total = c.at;
   return L;
 }

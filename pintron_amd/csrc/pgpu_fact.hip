@@ -28,6 +28,7 @@
 #include "pgpu_query_call.h"
 #include "pgpu_gaps.h"
 #include "pgpu_stage_launch.h"
+#include "pgpu_stage_drive.h"
 #include "pgpu_fact.h"
 
 namespace {
@@ -182,21 +183,13 @@ void fact_gather_kernel(const pgpu_chain_query* __restrict__ rq, const pgpu_chai
 
 thread_local double t_fact_ms = 0.0;
 
-struct EightEvents {
-  hipEvent_t e[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~EightEvents() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 }  // namespace
-
-#define DRIVE(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t pgpu_fact_drive(pgpu_ctx* ctx, pgpu_fact_job& d, const pgpu_fact_params& prm) {
   const uint32_t n = d.n, E = d.n_exons_total;
   const FactLayout L = fact_layout(n, E, pgpu_scan_tmp_bytes((size_t)n + 1));
   uint8_t* const B = d.block;
   hipStream_t st = pgpu_ctx_stream(ctx);
-  const auto rec = [&](int k) { return d.ev[k] ? hipEventRecord(d.ev[k], st) : hipSuccess; };
   pgpu_factor* const ex_in = (pgpu_factor*)(B + L.ex_in);
   pgpu_factor* const ex_clean = (pgpu_factor*)(B + L.ex_clean);
   pgpu_factor* const ex_gaps = (pgpu_factor*)(B + L.ex_gaps);
@@ -215,7 +208,7 @@ hipError_t pgpu_fact_drive(pgpu_ctx* ctx, pgpu_fact_job& d, const pgpu_fact_para
   const dim3 grid((n + 255) / 256), blk(256);
   d.total = 0; d.undersized = 0;
 
-  DRIVE(rec(0));
+  DRIVE(drive_record(d.ev, 0, st));
   const uint32_t need0[3] = { CLEAN_WS_DIRS_MIN, CLEAN_WS_ROWS_MIN, 0 };
   DRIVE(hipMemcpyAsync(need, need0, sizeof need0, hipMemcpyHostToDevice, st));
   if (E && d.cand_exons != ex_in) DRIVE(hipMemcpyAsync(ex_in, d.cand_exons, (size_t)E * sizeof(pgpu_factor), hipMemcpyDeviceToDevice, st));
@@ -236,26 +229,25 @@ hipError_t pgpu_fact_drive(pgpu_ctx* ctx, pgpu_fact_job& d, const pgpu_fact_para
   uint8_t* const ws = (uint8_t*)d.ws_alloc(d.ws_user, ws_clean > ws_chain ? ws_clean : ws_chain);
   if (!ws) return hipErrorOutOfMemory;
 
-  DRIVE(rec(2));
+  DRIVE(drive_record(d.ev, 2, st));
   pgpu_clean_launch(d.T, d.tlen, d.ests, ex_in, cq, n, ws, ws_dirs, ws_rows, waves_clean, ex_clean, B + L.marks, cr, need + 2, st);
-  DRIVE(rec(3));
+  DRIVE(drive_record(d.ev, 3, st));
   hipLaunchKernelGGL(fact_clean_to_gaps_kernel, grid, blk, 0, st, cq, cr, n, E, ex_clean, gq, res);
-  DRIVE(rec(4));
+  DRIVE(drive_record(d.ev, 4, st));
   pgpu_gaps_launch(d.T, d.ests, ex_clean, gq, n, waves, ex_gaps, B + L.gsteps, gr, st);
-  DRIVE(rec(5));
+  DRIVE(drive_record(d.ev, 5, st));
   hipLaunchKernelGGL(fact_gaps_to_refine_kernel, grid, blk, 0, st, gq, gr, n, E, ex_gaps, B + L.gsteps, prm, ex_kept, rq, res);
-  DRIVE(rec(6));
+  DRIVE(drive_record(d.ev, 6, st));
   pgpu_chain_launch(d.T, d.tlen, d.ests, ex_kept, rq, n, ws, waves, ex_refined, B + L.rsteps, rr, st);
-  DRIVE(rec(7));
+  DRIVE(drive_record(d.ev, 7, st));
   hipLaunchKernelGGL(fact_gather_kernel<false>, grid, blk, 0, st, rq, rr, n, res, counts, (const unsigned long long*)nullptr,
                      (const pgpu_factor*)nullptr, (const uint8_t*)nullptr, (pgpu_factor*)nullptr, (uint8_t*)nullptr);
-  DRIVE(hipMemsetAsync(counts + n, 0, sizeof(uint32_t), st));
-  pgpu_exclusive_scan_u32(counts, first, (size_t)n + 1, B + L.scan_tmp, st);
+  DRIVE(drive_scan(counts, first, n, B + L.scan_tmp, st));
   hipLaunchKernelGGL(fact_gather_kernel<true>, grid, blk, 0, st, rq, rr, n, res, (uint32_t*)nullptr, first, ex_refined, B + L.rsteps,
                      (pgpu_factor*)(B + L.out_exons), B + L.out_steps);
-  DRIVE(rec(1));
-  DRIVE(hipMemcpyAsync(&d.total, first + n, sizeof d.total, hipMemcpyDeviceToHost, st));
-  DRIVE(hipMemcpyAsync(&d.undersized, need + 2, sizeof d.undersized, hipMemcpyDeviceToHost, st));
+  DRIVE(drive_record(d.ev, 1, st));
+  DRIVE(hipMemcpyAsync(&d.total, first + n, sizeof d.total, hipMemcpyDeviceToHost, st));       // drive_total written out:
+  DRIVE(hipMemcpyAsync(&d.undersized, need + 2, sizeof d.undersized, hipMemcpyDeviceToHost, st));      // a second word comes back
   DRIVE(pgpu_ctx_wait(ctx));
   return hipGetLastError();
 }
@@ -271,9 +263,8 @@ extern "C" int pgpu_index_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, c
   if (!ctx || !idx || !params || !n_out || (n && (!q || !out)) || (ests_len && !ests) || (n_exons_total && !exons) ||
       (cap && (!out_exons || !out_steps)))
     return PGPU_EINVAL;
-  if (n > 0x7fffffffull || n_exons_total > 0x7fffffffull)
-    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 queries or exons in one call");
-  if (!fact_params_ok(*params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad factorization parameters (a suffpref length outside [0, 2^24])");
+  if (n > 0x7fffffffull || n_exons_total > 0x7fffffffull) return pgpu_ctx_fail(ctx, PGPU_EINVAL, FACT_TOO_MANY);
+  if (!fact_params_ok(*params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, FACT_BAD_PARAMS);
   NamedExons named;
   named.p = (uint8_t*)calloc(n_exons_total ? n_exons_total : 1, 1);
   if (!named.p) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "no memory for the table of the exons the queries name");
@@ -284,38 +275,38 @@ extern "C" int pgpu_index_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, c
   if (n == 0) return PGPU_OK;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   QueryCall call(ctx, "factorizations");
-  EightEvents ev;
   // the one device block: [ests + 64 | queries | the driver's block]; the workspace in a second one, once it is sized
   const FactLayout L = fact_layout(n, n_exons_total, pgpu_scan_tmp_bytes(n + 1));
-  const size_t o_q = up256(ests_len + 64), o_block = o_q + up256(n * sizeof *q);
-  TRY_HIP(hipMalloc((void**)&call.d, o_block + L.total));
-  if (pgpu_ctx_timing(ctx)) for (auto& e : ev.e) TRY_HIP(hipEventCreate(&e));
+  BlockCarver c{up256(ests_len + 64)};
+  const size_t o_q = c.take(n * sizeof *q), o_block = c.take(L.total);
+  TRY_HIP(hipMalloc((void**)&call.d, c.at));
+  TRY_HIP(call.timing_events(4));
   if (ests_len) TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, call.st));
   TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof *q, hipMemcpyHostToDevice, call.st));
   pgpu_fact_job job;
+  TRY_HIP(pgpu_fact_index_job(call, idx, o_q, o_block, exons, n_exons_total, n, job));
+  TRY_HIP(pgpu_fact_drive(ctx, job, *params));
+  if (job.undersized) return pgpu_clean_undersized(ctx, "factorizations");
+  *n_out = (size_t)job.total;
+  if (job.total > cap) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
+  TRY_HIP(drive_download(job.block, L, n * sizeof *out, job.total, out, out_exons, out_steps, call.st));
+  TRY_HIP(pgpu_ctx_wait(ctx));
+  call.elapsed_ms(0, &t_fact_ms);
+  return PGPU_OK;
+}
+
+hipError_t pgpu_fact_index_job(QueryCall& call, const pgpu_index* idx, size_t o_fq, size_t o_block, const pgpu_factor* exons,
+                               size_t n_exons_total, size_t n, pgpu_fact_job& job) {
   job.T = pgpu_index_genomic(idx); job.tlen = (uint32_t)pgpu_index_length(idx); job.ests = call.d;
-  job.fq = (const pgpu_fact_query*)(call.d + o_q); job.pat_off = nullptr; job.cand = nullptr;
-  job.block = call.d + o_block;
-  job.cand_exons = (const pgpu_factor*)(job.block + L.ex_in);          // uploaded where the driver wants them
-  if (n_exons_total) TRY_HIP(hipMemcpyAsync(job.block + L.ex_in, exons, n_exons_total * sizeof(pgpu_factor), hipMemcpyHostToDevice, call.st));
-  job.n = (uint32_t)n; job.n_exons_total = (uint32_t)n_exons_total;
+  job.fq = (const pgpu_fact_query*)(call.d + o_fq); job.pat_off = nullptr; job.cand = nullptr;
+  job.n = (uint32_t)n; job.n_exons_total = (uint32_t)n_exons_total; job.block = call.d + o_block;
+  uint8_t* const ex_in = job.block + fact_layout(n, n_exons_total, pgpu_scan_tmp_bytes(n + 1)).ex_in;
+  job.cand_exons = (const pgpu_factor*)ex_in;          // uploaded where the driver wants them
   job.ws_alloc = [](void* user, size_t bytes) -> void* {
     QueryCall* c = (QueryCall*)user;
     return hipMalloc((void**)&c->d2, bytes ? bytes : 16) == hipSuccess ? c->d2 : nullptr;
   };
   job.ws_user = &call;
-  for (int k = 0; k < 8; ++k) job.ev[k] = ev.e[k];
-  TRY_HIP(pgpu_fact_drive(ctx, job, *params));
-  if (job.undersized)
-    return pgpu_ctx_fail(ctx, PGPU_EDEVICE, "factorizations: the workspace of a wave was sized too small for an end-exon alignment");
-  *n_out = (size_t)job.total;
-  if (job.total > cap) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
-  TRY_HIP(hipMemcpyAsync(out, job.block + L.res, n * sizeof *out, hipMemcpyDeviceToHost, call.st));
-  if (job.total) {
-    TRY_HIP(hipMemcpyAsync(out_exons, job.block + L.out_exons, (size_t)job.total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, call.st));
-    TRY_HIP(hipMemcpyAsync(out_steps, job.block + L.out_steps, (size_t)job.total, hipMemcpyDeviceToHost, call.st));
-  }
-  TRY_HIP(pgpu_ctx_wait(ctx));
-  if (ev.e[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev.e[0], ev.e[1]); t_fact_ms = ms; }
-  return PGPU_OK;
+  for (int k = 0; k < 8; ++k) job.ev[k] = call.ev[k];
+  return n_exons_total ? hipMemcpyAsync(ex_in, exons, n_exons_total * sizeof(pgpu_factor), hipMemcpyHostToDevice, call.st) : hipSuccess;
 }

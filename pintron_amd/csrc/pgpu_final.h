@@ -55,16 +55,15 @@ struct FinalLayout {
 inline FinalLayout final_layout(size_t n, size_t n_exons_total, size_t scan_tmp_bytes) {
   const size_t ne = n_exons_total + n;
   FinalLayout L;
-  size_t at = 0;
-  const auto take = [&at](size_t bytes) { const size_t o = at; at += fact_up256(bytes ? bytes : 1); return o; };
-  L.ex_tin = take(ne * sizeof(pgpu_factor)); L.ex_tout = take(ne * sizeof(pgpu_factor));
-  L.ex_sin = take(ne * sizeof(pgpu_factor)); L.ex_sout = take(2 * ne * sizeof(pgpu_factor));
-  L.tsteps = take(ne); L.ssteps = take(2 * ne);
-  L.tq = take(n * sizeof(pgpu_tail_query)); L.tr = take(n * sizeof(pgpu_tail_result));
-  L.sq = take(n * sizeof(pgpu_small_query)); L.sr = take(n * sizeof(pgpu_small_result));
-  L.res = take(n * sizeof(pgpu_final_result));
-  L.counts = take((n + 1) * sizeof(uint32_t)); L.first = take((n + 1) * sizeof(uint64_t)); L.scan_tmp = take(scan_tmp_bytes);
-  L.out_exons = take(2 * n_exons_total * sizeof(pgpu_factor)); L.out_steps = take(2 * n_exons_total);
-  L.total = at;
+  BlockCarver c;
+  L.ex_tin = c.take(ne * sizeof(pgpu_factor)); L.ex_tout = c.take(ne * sizeof(pgpu_factor));
+  L.ex_sin = c.take(ne * sizeof(pgpu_factor)); L.ex_sout = c.take(2 * ne * sizeof(pgpu_factor));
+  L.tsteps = c.take(ne); L.ssteps = c.take(2 * ne);
+  L.tq = c.take(n * sizeof(pgpu_tail_query)); L.tr = c.take(n * sizeof(pgpu_tail_result));
+  L.sq = c.take(n * sizeof(pgpu_small_query)); L.sr = c.take(n * sizeof(pgpu_small_result));
+  L.res = c.take(n * sizeof(pgpu_final_result));
+  L.counts = c.take((n + 1) * sizeof(uint32_t)); L.first = c.take((n + 1) * sizeof(uint64_t)); L.scan_tmp = c.take(scan_tmp_bytes);
+  L.out_exons = c.take(2 * n_exons_total * sizeof(pgpu_factor)); L.out_steps = c.take(2 * n_exons_total);
+  L.total = c.at;
   return L;
 }

@@ -29,6 +29,7 @@
 #include "pgpu_classify.h"
 #include "pgpu_small.h"
 #include "pgpu_stage_launch.h"
+#include "pgpu_stage_drive.h"
 #include "pgpu_final.h"
 
 namespace {
@@ -153,14 +154,7 @@ void final_gather_kernel(const pgpu_small_query* __restrict__ sq, const pgpu_sma
 
 thread_local double t_final_ms = 0.0;
 
-struct FinalEvents {
-  hipEvent_t e[14] = {nullptr};      // the eight of pgpu_fact_job, the six of pgpu_final_job
-  ~FinalEvents() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 }  // namespace
-
-#define DRIVE(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& d) {
   const uint32_t n = d.n, E = d.n_exons_total;
@@ -171,7 +165,6 @@ hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& d) {
   const FinalLayout L = final_layout(n, E, scan_tmp);
   uint8_t* const B = d.block;
   hipStream_t st = pgpu_ctx_stream(ctx);
-  const auto rec = [&](int k) { return d.ev[k] ? hipEventRecord(d.ev[k], st) : hipSuccess; };
   pgpu_factor* const ex_tin = (pgpu_factor*)(B + L.ex_tin);
   pgpu_factor* const ex_tout = (pgpu_factor*)(B + L.ex_tout);
   pgpu_factor* const ex_sin = (pgpu_factor*)(B + L.ex_sin);
@@ -188,34 +181,31 @@ hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& d) {
   size_t waves = 0, cus = 0;
   DRIVE(chained_waves(n, waves, cus));
 
-  DRIVE(rec(0));
+  DRIVE(drive_record(d.ev, 0, st));
   hipLaunchKernelGGL(final_to_tail_kernel, grid, blk, 0, st, d.fq, d.pat_off, d.orig_off, (const pgpu_fact_result*)(d.fact_block + F.res),
                      (const pgpu_factor*)(d.fact_block + F.out_exons), n, E, d.ests_len, tlen, ex_tin, tq, res);
-  DRIVE(rec(2));
+  DRIVE(drive_record(d.ev, 2, st));
   if (d.given_tail) {
     DRIVE(hipMemcpyAsync(tr, d.given_tail->results, n * sizeof *tr, hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(ex_tout, d.given_tail->exons, ((size_t)E + n) * sizeof(pgpu_factor), hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(B + L.tsteps, d.given_tail->steps, (size_t)E + n, hipMemcpyHostToDevice, st));
   } else pgpu_tail_launch(d.ix.T, tlen, d.ests, ex_tin, tq, n, waves, ex_tout, B + L.tsteps, tr, st);
-  DRIVE(rec(3));
+  DRIVE(drive_record(d.ev, 3, st));
   hipLaunchKernelGGL(final_tail_to_small_kernel, grid, blk, 0, st, tq, tr, n, E, d.ests_len, tlen, ex_tout, B + L.tsteps, ex_sin, sq, res);
-  DRIVE(rec(4));
+  DRIVE(drive_record(d.ev, 4, st));
   if (d.given_small) {
     DRIVE(hipMemcpyAsync(sr, d.given_small->results, n * sizeof *sr, hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(ex_sout, d.given_small->exons, 2 * ((size_t)E + n) * sizeof(pgpu_factor), hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(B + L.ssteps, d.given_small->steps, 2 * ((size_t)E + n), hipMemcpyHostToDevice, st));
   } else pgpu_small_launch(d.ix, *d.cv, d.ests, ex_sin, sq, n, d.min_intron_length, waves, ex_sout, B + L.ssteps, sr, st);
-  DRIVE(rec(5));
+  DRIVE(drive_record(d.ev, 5, st));
   hipLaunchKernelGGL(final_gather_kernel<false>, grid, blk, 0, st, sq, sr, n, res, counts, (const unsigned long long*)nullptr,
                      (const pgpu_factor*)nullptr, (const uint8_t*)nullptr, (pgpu_factor*)nullptr, (uint8_t*)nullptr);
-  DRIVE(hipMemsetAsync(counts + n, 0, sizeof(uint32_t), st));
-  pgpu_exclusive_scan_u32(counts, first, (size_t)n + 1, B + L.scan_tmp, st);
+  DRIVE(drive_scan(counts, first, n, B + L.scan_tmp, st));
   hipLaunchKernelGGL(final_gather_kernel<true>, grid, blk, 0, st, sq, sr, n, res, (uint32_t*)nullptr, first, ex_sout, B + L.ssteps,
                      (pgpu_factor*)(B + L.out_exons), B + L.out_steps);
-  DRIVE(rec(1));
-  DRIVE(hipMemcpyAsync(&d.total, first + n, sizeof d.total, hipMemcpyDeviceToHost, st));
-  DRIVE(pgpu_ctx_wait(ctx));
-  return hipGetLastError();
+  DRIVE(drive_record(d.ev, 1, st));
+  return drive_total(ctx, first, n, &d.total);
 }
 
 extern "C" double pgpu_index_final_factorizations_kernel_ms(void) { return t_final_ms; }
@@ -230,10 +220,9 @@ extern "C" int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* 
   if (!ctx || !idx || !params || !small_params || !n_out || (n && (!q || !out)) || (ests_len && !ests) ||
       (n_exons_total && !exons) || (cap && (!out_exons || !out_steps)))
     return PGPU_EINVAL;
-  if (n > 0x7fffffffull || n_exons_total > 0x7fffffffull)
-    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 queries or exons in one call");
-  if (!fact_params_ok(*params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad factorization parameters (a suffpref length outside [0, 2^24])");
-  if (!small_params_ok(small_params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad small-chains parameters (reserved != 0)");
+  if (n > 0x7fffffffull || n_exons_total > 0x7fffffffull) return pgpu_ctx_fail(ctx, PGPU_EINVAL, FACT_TOO_MANY);
+  if (!fact_params_ok(*params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, FACT_BAD_PARAMS);
+  if (!small_params_ok(small_params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, SMALL_BAD_PARAMS);
   NamedExons named;
   named.p = (uint8_t*)calloc(n_exons_total ? n_exons_total : 1, 1);
   const std::unique_ptr<pgpu_fact_query, void (*)(void*)> fact_queries((pgpu_fact_query*)calloc(n ? n : 1, sizeof(pgpu_fact_query)), free);
@@ -246,59 +235,37 @@ extern "C" int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* 
   if (n == 0) return PGPU_OK;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   ClassView cv;
-  const int rc = pgpu_class_view_get(ctx, idx, &cv);
-  if (rc != PGPU_OK) return rc;
+  if (const int rc = pgpu_class_view_get(ctx, idx, &cv)) return rc;
   QueryCall call(ctx, "final factorizations");
-  FinalEvents ev;
   // the one device block: [ests + 64 | final queries | factorization queries | the first driver's block | the second one's];
   // the workspace of clean and refine in a second one, once it is sized
   const size_t scan_tmp = pgpu_scan_tmp_bytes(n + 1);
   const FactLayout F = fact_layout(n, n_exons_total, scan_tmp);
   const FinalLayout L = final_layout(n, n_exons_total, scan_tmp);
-  const size_t o_q = up256(ests_len + 64), o_fq = o_q + up256(n * sizeof *q), o_fact = o_fq + up256(n * sizeof *fq),
-               o_final = o_fact + F.total;
-  TRY_HIP(hipMalloc((void**)&call.d, o_final + L.total));
-  if (pgpu_ctx_timing(ctx)) for (auto& e : ev.e) TRY_HIP(hipEventCreate(&e));
+  BlockCarver c{up256(ests_len + 64)};
+  const size_t o_q = c.take(n * sizeof *q), o_fq = c.take(n * sizeof *fq), o_fact = c.take(F.total), o_final = c.take(L.total);
+  TRY_HIP(hipMalloc((void**)&call.d, c.at));
+  TRY_HIP(call.timing_events(7));                      // the eight of pgpu_fact_job, then the six of pgpu_final_job
   if (ests_len) TRY_HIP(hipMemcpyAsync(call.d, ests, ests_len, hipMemcpyHostToDevice, call.st));
   TRY_HIP(hipMemcpyAsync(call.d + o_q, q, n * sizeof *q, hipMemcpyHostToDevice, call.st));
   TRY_HIP(hipMemcpyAsync(call.d + o_fq, fq, n * sizeof *fq, hipMemcpyHostToDevice, call.st));
   pgpu_fact_job job;
-  job.T = pgpu_index_genomic(idx); job.tlen = (uint32_t)pgpu_index_length(idx); job.ests = call.d;
-  job.fq = (const pgpu_fact_query*)(call.d + o_fq); job.pat_off = nullptr; job.cand = nullptr;
-  job.block = call.d + o_fact;
-  job.cand_exons = (const pgpu_factor*)(job.block + F.ex_in);          // uploaded where the driver wants them
-  if (n_exons_total) TRY_HIP(hipMemcpyAsync(job.block + F.ex_in, exons, n_exons_total * sizeof(pgpu_factor), hipMemcpyHostToDevice, call.st));
-  job.n = (uint32_t)n; job.n_exons_total = (uint32_t)n_exons_total;
-  job.ws_alloc = [](void* user, size_t bytes) -> void* {
-    QueryCall* c = (QueryCall*)user;
-    return hipMalloc((void**)&c->d2, bytes ? bytes : 16) == hipSuccess ? c->d2 : nullptr;
-  };
-  job.ws_user = &call;
-  for (int k = 0; k < 8; ++k) job.ev[k] = ev.e[k];
+  TRY_HIP(pgpu_fact_index_job(call, idx, o_fq, o_fact, exons, n_exons_total, n, job));
   TRY_HIP(pgpu_fact_drive(ctx, job, *params));
-  if (job.undersized)
-    return pgpu_ctx_fail(ctx, PGPU_EDEVICE, "final factorizations: the workspace of a wave was sized too small for an end-exon alignment");
+  if (job.undersized) return pgpu_clean_undersized(ctx, "final factorizations");
   pgpu_final_job fin;
-  fin.ix = pgpu_index_lcf_view(idx);
-  if (!fin.ix.focc || !fin.ix.rmq) fin.ix.first_bad = 0;      // as pgpu_index_small_chains: every prefix question is refused = 3
-  fin.cv = &cv;
+  fin.ix = pgpu_index_small_view(idx); fin.cv = &cv;
   fin.ests = call.d; fin.ests_len = ests_len;
   fin.fq = (const pgpu_final_query*)(call.d + o_q); fin.pat_off = nullptr; fin.orig_off = nullptr;
-  fin.fact_block = job.block;
-  fin.n = (uint32_t)n; fin.n_exons_total = (uint32_t)n_exons_total;
-  fin.min_intron_length = small_params->min_intron_length;
-  fin.block = call.d + o_final;
-  for (int k = 0; k < 6; ++k) fin.ev[k] = ev.e[8 + k];
+  fin.n = (uint32_t)n; fin.n_exons_total = (uint32_t)n_exons_total; fin.min_intron_length = small_params->min_intron_length;
+  fin.fact_block = job.block; fin.block = call.d + o_final;
+  for (int k = 0; k < 6; ++k) fin.ev[k] = call.ev[8 + k];
   TRY_HIP(pgpu_final_drive(ctx, fin));
   *n_out = (size_t)fin.total;
   if (fin.total > cap) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
-  TRY_HIP(hipMemcpyAsync(out, fin.block + L.res, n * sizeof *out, hipMemcpyDeviceToHost, call.st));
-  if (fin.total) {
-    TRY_HIP(hipMemcpyAsync(out_exons, fin.block + L.out_exons, (size_t)fin.total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, call.st));
-    TRY_HIP(hipMemcpyAsync(out_steps, fin.block + L.out_steps, (size_t)fin.total, hipMemcpyDeviceToHost, call.st));
-  }
+  TRY_HIP(drive_download(fin.block, L, n * sizeof *out, fin.total, out, out_exons, out_steps, call.st));
   TRY_HIP(pgpu_ctx_wait(ctx));
-  if (ev.e[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev.e[0], ev.e[9]); t_final_ms = ms; }
+  if (call.ev[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, call.ev[0], call.ev[9]); t_final_ms = ms; }
   return PGPU_OK;
 }
 
@@ -354,11 +321,7 @@ extern "C" int pgpu_final_handoffs_probe(pgpu_ctx* ctx, uint32_t tlen, size_t es
   TRY_HIP(hipMemcpyAsync(tq, fin.block + L.tq, n * sizeof *tq, hipMemcpyDeviceToHost, call.st));
   TRY_HIP(hipMemcpyAsync(sq, fin.block + L.sq, n * sizeof *sq, hipMemcpyDeviceToHost, call.st));
   TRY_HIP(hipMemcpyAsync(ex_sin, fin.block + L.ex_sin, (n_exons_total + n) * sizeof(pgpu_factor), hipMemcpyDeviceToHost, call.st));
-  TRY_HIP(hipMemcpyAsync(out, fin.block + L.res, n * sizeof *out, hipMemcpyDeviceToHost, call.st));
-  if (fin.total) {
-    TRY_HIP(hipMemcpyAsync(out_exons, fin.block + L.out_exons, (size_t)fin.total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, call.st));
-    TRY_HIP(hipMemcpyAsync(out_steps, fin.block + L.out_steps, (size_t)fin.total, hipMemcpyDeviceToHost, call.st));
-  }
+  TRY_HIP(drive_download(fin.block, L, n * sizeof *out, fin.total, out, out_exons, out_steps, call.st));
   TRY_HIP(pgpu_ctx_wait(ctx));
   return PGPU_OK;
 }

@@ -2,6 +2,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <cstdio>
+#include <cstdlib>
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include "../../include/pintron_gpu.h"
@@ -42,6 +44,12 @@ struct LcfIndexView {
   uint32_t n, levels, first_bad;
 };
 LcfIndexView pgpu_index_lcf_view(const pgpu_index* idx);
+// the small stage's view (pgpu_index_small_chains, pgpu_final_job): without the derived tables every prefix question is refused = 3
+inline LcfIndexView pgpu_index_small_view(const pgpu_index* idx) {
+  LcfIndexView ix = pgpu_index_lcf_view(idx);
+  if (!ix.focc || !ix.rmq) ix.first_bad = 0;
+  return ix;
+}
 constexpr uint32_t LCF_FOCC_ENTRIES = 87380;      // 4 + 16 + ... + 4^8
 
 // What the pairing kernels need (pgpu_pairing_plan.hip): the sequence T (n bytes), its suffix array and LCP array
@@ -136,10 +144,16 @@ struct pgpu_fact_job {
   uint32_t n, n_exons_total;
   uint8_t* block;
   void* (*ws_alloc)(void* user, size_t bytes); void* ws_user;
-  hipEvent_t ev[8];            // null without timing: 0-1 the whole drive, 2-3 clean_kernel, 4-5 gaps_kernel, 6-7 chain_kernel
+  hipEvent_t ev[8];            // the caller's (QueryCall, plan); null without timing: 0-1 the whole drive, 2-3 clean, 4-5 gaps, 6-7 chain
   unsigned long long total; uint32_t undersized;
 };
 hipError_t pgpu_fact_drive(pgpu_ctx* ctx, pgpu_fact_job& job, const pgpu_fact_params& prm);
+// what an entry answers to a job that comes back `undersized`; `what`: the entry's noun
+inline int pgpu_clean_undersized(pgpu_ctx* ctx, const char* what) {
+  char msg[128];
+  snprintf(msg, sizeof msg, "%s: the workspace of a wave was sized too small for an end-exon alignment", what);
+  return pgpu_ctx_fail(ctx, PGPU_EDEVICE, msg);
+}
 // pgpu_final.hip: the answer of pgpu_fact_drive, where it lies (`fact_block`, the block of a job of the same n and
 // n_exons_total, read only), through the tail and the small stage.  The ESTs are either the queries of the index form (fq) or
 // a plan's pattern offsets and its table of original offsets (pat_off, orig_off; fq null); `ests_len` bytes lie behind
@@ -184,8 +198,6 @@ struct pgpu_unit_job {
 };
 hipError_t pgpu_unit_drive(pgpu_ctx* ctx, pgpu_unit_job& job);
 // PGPU_TRACE_ALLOC=1: every page-locked host allocation of the library on stderr (size, address, call site)
-#include <cstdio>
-#include <cstdlib>
 static inline void pgpu_trace_alloc(const char* what, const void* q, size_t bytes) {
   static int on = -1;
   if (on < 0) { const char* e = getenv("PGPU_TRACE_ALLOC"); on = (e && *e && *e != '0') ? 1 : 0; }

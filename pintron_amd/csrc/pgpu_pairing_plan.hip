@@ -19,6 +19,7 @@
 #include <new>
 
 #include "pgpu_index.h"
+#include "pgpu_stage_drive.h"
 #include "pgpu_fact.h"
 #include "pgpu_final.h"
 #include "pgpu_unit.h"
@@ -511,20 +512,25 @@ static hipError_t plan_events(pgpu_pairing_plan* p, int first, int count) {
   }
   return hipSuccess;
 }
-static hipError_t record(const pgpu_pairing_plan* p, int k, hipStream_t st) { return p->ev[k] ? hipEventRecord(p->ev[k], st) : hipSuccess; }
 
-// A count pass has written counts[0..n): counts[n] = 0, offsets = the exclusive prefix sums of the n + 1, and *total =
-// offsets[n] on the host, waited for.  `ev` (may be null) is recorded behind the scan, where the pairing stages end
-// their count+scan time.
+// A count pass has written counts[0..n): drive_scan into offsets, and *total = offsets[n] on the host, waited for.  `ev` (may
+// be null) is recorded behind the scan, where the pairing stages end their count+scan time.
 static hipError_t scan_total(pgpu_ctx* ctx, const pgpu_pairing_plan* p, uint32_t* counts, unsigned long long* offsets, size_t n,
                              hipEvent_t ev, unsigned long long* total) {
   hipStream_t st = pgpu_ctx_stream(ctx);
-  hipError_t e = hipMemsetAsync(counts + n, 0, sizeof(uint32_t), st);
-  if (e != hipSuccess) return e;
-  pgpu_exclusive_scan_u32(counts, offsets, n + 1, p->d_tmp, st);
-  if (ev && (e = hipEventRecord(ev, st)) != hipSuccess) return e;
-  e = hipMemcpyAsync(total, offsets + n, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : pgpu_ctx_wait(ctx);
+  DRIVE(drive_scan(counts, offsets, n, p->d_tmp, st));
+  if (ev) DRIVE(hipEventRecord(ev, st));
+  DRIVE(hipMemcpyAsync(total, offsets + n, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  return pgpu_ctx_wait(ctx);
+}
+
+// the one block of a rung from four to six, with an eighth to spare; a resident plan takes it anew: the pool may have moved
+static uint8_t* stage_block(pgpu_pairing_plan* p, uint8_t* ptr, size_t* cap, size_t total, PlanSlot slot) {
+  return plan_grow(p, p->resident ? nullptr : ptr, cap, total, total / 8, slot);
+}
+// after the wait: the times between `pairs` pairs of events from ev[first] on, when the plan has them
+static void elapsed_pairs(const pgpu_pairing_plan* p, int first, int pairs, float* ms) {
+  if (p->ev[first]) for (int k = 0; k < pairs; ++k) hipEventElapsedTime(&ms[k], p->ev[first + 2 * k], p->ev[first + 2 * k + 1]);
 }
 
 static void pairing_plan_free(pgpu_pairing_plan* p) {
@@ -566,10 +572,9 @@ static int pairing_plan_create(pgpu_ctx* ctx, const pgpu_index* idx, const char*
   p->pooled = p->resident || pgpu_ctx_pool_acquire(ctx, PLAN_POOL);
   p->tmp_bytes = pgpu_scan_tmp_bytes(std::max(tp, n_pat) + 1);
   if (p->resident) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_off = up(tp + orig_total + 64), o_code = o_off + up((n_pat + 1) * sizeof(unsigned long long)),
-                 o_bad = o_code + up((2 * bad_words + 4) * sizeof(uint32_t)), o_orig = o_bad + up((bad_words + 4) * sizeof(uint32_t)),
-                 total = o_orig + (n_orig ? up(n_pat * sizeof(unsigned long long)) : 0);
+    const size_t o_off = up256(tp + orig_total + 64), o_code = o_off + up256((n_pat + 1) * sizeof(unsigned long long)),
+                 o_bad = o_code + up256((2 * bad_words + 4) * sizeof(uint32_t)), o_orig = o_bad + up256((bad_words + 4) * sizeof(uint32_t)),
+                 total = o_orig + (n_orig ? up256(n_pat * sizeof(unsigned long long)) : 0);
     PLAN_TRY(hipMalloc(&p->d_resident, total));
     pgpu_trace_alloc("resident plan", p->d_resident, total);
     uint8_t* base = (uint8_t*)p->d_resident;
@@ -651,25 +656,25 @@ extern "C" int pgpu_pairing_plan_run(pgpu_ctx* ctx, pgpu_pairing_plan* p, const 
   const PackedSeq Tp{ix.code, ix.bad}, Pp{p->d_pcode, p->d_pbad};
   const dim3 pgrid((unsigned)p->n_pat), pblk(64);
   const ProfRange range("pairings");
-  PLAN_TRY(record(p, 0, st));
+  PLAN_TRY(drive_record(p->ev, 0, st));
   hipLaunchKernelGGL(pair_locate_kernel, pgrid, pblk, 0, st, ix.T, ix.n, ix.sa, ix.klo, ix.khi, p->d_pats, p->d_pat_off, prm, p->d_lo, p->d_hi, p->d_a, Tp, Pp);
-  PLAN_TRY(record(p, 1, st));
+  PLAN_TRY(drive_record(p->ev, 1, st));
   hipLaunchKernelGGL(pair_chain_kernel, dim3((unsigned)((p->n_pat + 63) / 64)), pblk, 0, st, ix.T, ix.n, ix.sa, ix.lcp,
                      p->d_pats, p->d_pat_off, (uint32_t)p->n_pat, prm, p->d_lo, p->d_hi, p->d_a, p->d_thr, Tp, Pp);
-  PLAN_TRY(record(p, 2, st));
+  PLAN_TRY(drive_record(p->ev, 2, st));
   hipLaunchKernelGGL(pair_count_kernel, pgrid, pblk, 0, st, ix.T, ix.n, ix.sa, ix.key, ix.sigma, p->d_pats, p->d_pat_off, prm, p->d_lo, p->d_hi, p->d_thr, p->d_cnt, Tp, Pp);
   PLAN_TRY(scan_total(ctx, p, p->d_cnt, p->d_cand_off, tp, p->ev[3], &p->n_cand));
   PLAN_NEED(p->d_cand = plan_grow(p, p->d_cand, &p->cand_cap, (size_t)p->n_cand, (size_t)p->n_cand / 8 + 1024, SLOT_CAND));
   PLAN_NEED(p->d_keep = plan_grow(p, p->d_keep, &p->keep_cap, (size_t)p->n_cand, (size_t)p->n_cand / 8 + 1024, SLOT_KEEP));
   hipLaunchKernelGGL(pair_fill_kernel, pgrid, pblk, 0, st, ix.T, ix.n, ix.sa, ix.key, ix.sigma, p->d_pats, p->d_pat_off, prm, p->d_lo, p->d_hi, p->d_thr,
                      p->d_cand_off, p->d_cand, p->d_cnt_a, Tp, Pp);
-  PLAN_TRY(record(p, 4, st));
+  PLAN_TRY(drive_record(p->ev, 4, st));
   hipLaunchKernelGGL(pair_cross_kernel, pgrid, pblk, 0, st, p->d_pat_off, p->d_cand_off, p->d_cand, p->d_cnt_a, p->d_keep, p->d_cnt_b);
   PLAN_TRY(scan_total(ctx, p, p->d_cnt_b, p->d_out_off, tp, p->ev[5], &p->n_out));
   PLAN_NEED(p->d_out = plan_grow(p, p->d_out, &p->out_cap, (size_t)p->n_out, (size_t)p->n_out / 8 + 1024, SLOT_OUT));
   hipLaunchKernelGGL(pair_emit_kernel, pgrid, pblk, 0, st, p->d_pat_off, p->d_cand_off, p->d_cand, p->d_cnt_a, p->d_keep, p->d_out_off,
                      p->d_out, p->d_out_first, (uint32_t)p->n_pat, p->total_pos);
-  PLAN_TRY(record(p, 6, st));
+  PLAN_TRY(drive_record(p->ev, 6, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   PLAN_TRY(hipGetLastError());
   if (p->ev[0]) for (int k = 0; k < 6; ++k) hipEventElapsedTime(&p->ms[k], p->ev[k], p->ev[k + 1]);
@@ -716,15 +721,15 @@ extern "C" int pgpu_pairing_plan_run_meg(pgpu_ctx* ctx, pgpu_pairing_plan* p, co
     PLAN_NEED(p->d_meg_off = plan_alloc<unsigned long long>(p, SLOT_MEG_OFF, (size_t)np + 1));
     PLAN_TRY(plan_events(p, EV_MEG, 2));
   }
-  PLAN_TRY(record(p, EV_MEG, st));
+  PLAN_TRY(drive_record(p->ev, EV_MEG, st));
   pgpu_meg_launch_build(p->d_out, p->d_out_first, p->d_pat_off, np, prm, p->d_meg_scratch, p->d_meg_info, p->d_meg_bytes, st);
   PLAN_TRY(scan_total(ctx, p, p->d_meg_bytes, p->d_meg_off, np, nullptr, &p->meg_total));
   PLAN_NEED(p->d_meg_out = plan_grow(p, p->d_meg_out, &p->meg_cap, (size_t)p->meg_total, (size_t)p->meg_total / 8 + 4096, SLOT_MEG_OUT));
   pgpu_meg_launch_emit(np, p->d_meg_scratch, p->d_meg_info, p->d_meg_off, p->d_meg_out, st);
-  PLAN_TRY(record(p, EV_MEG + 1, st));
+  PLAN_TRY(drive_record(p->ev, EV_MEG + 1, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   PLAN_TRY(hipGetLastError());
-  if (p->ev[EV_MEG]) hipEventElapsedTime(&p->meg_ms, p->ev[EV_MEG], p->ev[EV_MEG + 1]);
+  elapsed_pairs(p, EV_MEG, 1, &p->meg_ms);
   p->meg_L = prm->min_factor_len;
   return reached(p, RECORDS);
 }
@@ -769,16 +774,16 @@ extern "C" int pgpu_pairing_plan_run_candidates(pgpu_ctx* ctx, pgpu_pairing_plan
     PLAN_NEED(p->d_cand_first = plan_alloc<unsigned long long>(p, SLOT_CAND_FIRST, (size_t)np + 1));
     PLAN_TRY(plan_events(p, EV_CAND, 2));
   }
-  PLAN_TRY(record(p, EV_CAND, st));
+  PLAN_TRY(drive_record(p->ev, EV_CAND, st));
   pgpu_cand_launch_count(p->d_meg_out, p->d_meg_off, np, ix.T, ix.n, prm, p->d_cand_res, p->d_cand_cnt, st);
   unsigned long long total = 0;
   PLAN_TRY(scan_total(ctx, p, p->d_cand_cnt, p->d_cand_first, np, nullptr, &total));
   PLAN_NEED(p->d_cand_exons = plan_grow(p, p->d_cand_exons, &p->cand_exons_cap, (size_t)total, (size_t)total / 8 + 256, SLOT_CAND_EXONS));
   pgpu_cand_launch_write(p->d_meg_out, p->d_meg_off, np, ix.T, ix.n, prm, p->d_cand_res, p->d_cand_first, p->d_cand_exons, st);
-  PLAN_TRY(record(p, EV_CAND + 1, st));
+  PLAN_TRY(drive_record(p->ev, EV_CAND + 1, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   PLAN_TRY(hipGetLastError());
-  if (p->ev[EV_CAND]) hipEventElapsedTime(&p->cand_ms, p->ev[EV_CAND], p->ev[EV_CAND + 1]);
+  elapsed_pairs(p, EV_CAND, 1, &p->cand_ms);
   p->cand_total = total;
   return reached(p, CANDIDATES);
 }
@@ -807,7 +812,7 @@ extern "C" int pgpu_pairing_plan_run_factorizations(pgpu_ctx* ctx, pgpu_pairing_
   p->fact_total = 0;
   for (auto& m : p->fact_ms) m = 0.f;
   lower(p, CANDIDATES);
-  if (!fact_params_ok(*prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad factorization parameters (a suffpref length outside [0, 2^24])");
+  if (!fact_params_ok(*prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, FACT_BAD_PARAMS);
   if (p->stage < CANDIDATES)
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_factorizations needs the candidates of pgpu_pairing_plan_run_candidates");
   if (p->n_pat == 0) return reached(p, FACTORIZATIONS);
@@ -815,10 +820,10 @@ extern "C" int pgpu_pairing_plan_run_factorizations(pgpu_ctx* ctx, pgpu_pairing_
   if (p->n_pat > 0x7fffffffull || p->cand_total > 0x7fffffffull)          // as the index form: exon indices are 32 bits wide
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 patterns or candidate exons in one plan");
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
-  if (p->resident) { p->d_fact = nullptr; p->d_fact_ws = nullptr; }            // taken anew: the pool may have moved
+  if (p->resident) p->d_fact_ws = nullptr;                                     // taken anew, as the block: the pool may have moved
   const ProfRange range("factorizations");
   const FactLayout L = fact_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
-  PLAN_NEED(p->d_fact = plan_grow(p, p->d_fact, &p->fact_cap, L.total, L.total / 8, SLOT_FACT));
+  PLAN_NEED(p->d_fact = stage_block(p, p->d_fact, &p->fact_cap, L.total, SLOT_FACT));
   PLAN_TRY(plan_events(p, EV_FACT, 8));
   pgpu_fact_job job;
   job.T = p->ix.T; job.tlen = p->ix.n; job.ests = p->d_pats;
@@ -832,10 +837,9 @@ extern "C" int pgpu_pairing_plan_run_factorizations(pgpu_ctx* ctx, pgpu_pairing_
   job.ws_user = p;
   for (int k = 0; k < 8; ++k) job.ev[k] = p->ev[EV_FACT + k];
   PLAN_TRY(pgpu_fact_drive(ctx, job, *prm));
-  if (job.undersized)
-    return pgpu_ctx_fail(ctx, PGPU_EDEVICE, "factorizations: the workspace of a wave was sized too small for an end-exon alignment");
+  if (job.undersized) return pgpu_clean_undersized(ctx, "factorizations");
   p->fact_total = job.total;
-  if (p->ev[EV_FACT]) for (int k = 0; k < 4; ++k) hipEventElapsedTime(&p->fact_ms[k], p->ev[EV_FACT + 2 * k], p->ev[EV_FACT + 2 * k + 1]);
+  elapsed_pairs(p, EV_FACT, 4, p->fact_ms);
   return reached(p, FACTORIZATIONS);
 }
 
@@ -854,11 +858,7 @@ extern "C" int pgpu_pairing_plan_fetch_factorizations(pgpu_ctx* ctx, pgpu_pairin
   hipStream_t st = pgpu_ctx_stream(ctx);
   if (p->n_pat == 0) return PGPU_OK;
   const FactLayout L = fact_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
-  PLAN_TRY(hipMemcpyAsync(out, p->d_fact + L.res, p->n_pat * sizeof(pgpu_fact_result), hipMemcpyDeviceToHost, st));
-  if (p->fact_total) {
-    PLAN_TRY(hipMemcpyAsync(exons, p->d_fact + L.out_exons, (size_t)p->fact_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
-    PLAN_TRY(hipMemcpyAsync(steps, p->d_fact + L.out_steps, (size_t)p->fact_total, hipMemcpyDeviceToHost, st));
-  }
+  PLAN_TRY(drive_download(p->d_fact, L, p->n_pat * sizeof *out, p->fact_total, out, exons, steps, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   return PGPU_OK;
 }
@@ -869,7 +869,7 @@ extern "C" int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pa
   p->final_total = 0;
   for (auto& m : p->final_ms) m = 0.f;
   lower(p, FACTORIZATIONS);
-  if (!small_params_ok(prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad small-chains parameters (reserved != 0)");
+  if (!small_params_ok(prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, SMALL_BAD_PARAMS);
   if (p->stage < FACTORIZATIONS)
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_final_factorizations needs the factorizations of pgpu_pairing_plan_run_factorizations");
   if (p->n_pat == 0) return reached(p, FINALS);
@@ -877,25 +877,20 @@ extern "C" int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pa
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   ClassView cv;
   if (const int rc = pgpu_class_view_get(ctx, p->idx, &cv)) return rc;
-  if (p->resident) p->d_final = nullptr;                                       // taken anew: the pool may have moved
   const ProfRange range("final factorizations");
   const FinalLayout L = final_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
-  PLAN_NEED(p->d_final = plan_grow(p, p->d_final, &p->final_cap, L.total, L.total / 8, SLOT_FINAL));
+  PLAN_NEED(p->d_final = stage_block(p, p->d_final, &p->final_cap, L.total, SLOT_FINAL));
   PLAN_TRY(plan_events(p, EV_FINAL, 6));
   pgpu_final_job job;
-  job.ix = pgpu_index_lcf_view(p->idx);
-  if (!job.ix.focc || !job.ix.rmq) job.ix.first_bad = 0;      // as pgpu_index_small_chains: every prefix question is refused = 3
-  job.cv = &cv;
+  job.ix = pgpu_index_small_view(p->idx); job.cv = &cv;
   job.ests = p->d_pats; job.ests_len = p->seq_bytes;
   job.fq = nullptr; job.pat_off = p->d_pat_off; job.orig_off = p->d_orig_off;
-  job.fact_block = p->d_fact;
-  job.n = (uint32_t)p->n_pat; job.n_exons_total = (uint32_t)p->cand_total;
-  job.min_intron_length = prm->min_intron_length;
-  job.block = p->d_final;
+  job.n = (uint32_t)p->n_pat; job.n_exons_total = (uint32_t)p->cand_total; job.min_intron_length = prm->min_intron_length;
+  job.fact_block = p->d_fact; job.block = p->d_final;
   for (int k = 0; k < 6; ++k) job.ev[k] = p->ev[EV_FINAL + k];
   PLAN_TRY(pgpu_final_drive(ctx, job));
   p->final_total = job.total;
-  if (p->ev[EV_FINAL]) for (int k = 0; k < 3; ++k) hipEventElapsedTime(&p->final_ms[k], p->ev[EV_FINAL + 2 * k], p->ev[EV_FINAL + 2 * k + 1]);
+  elapsed_pairs(p, EV_FINAL, 3, p->final_ms);
   return reached(p, FINALS);
 }
 
@@ -913,11 +908,7 @@ extern "C" int pgpu_pairing_plan_fetch_final_factorizations(pgpu_ctx* ctx, pgpu_
   hipStream_t st = pgpu_ctx_stream(ctx);
   if (p->n_pat == 0) return PGPU_OK;
   const FinalLayout L = final_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
-  PLAN_TRY(hipMemcpyAsync(out, p->d_final + L.res, p->n_pat * sizeof(pgpu_final_result), hipMemcpyDeviceToHost, st));
-  if (p->final_total) {
-    PLAN_TRY(hipMemcpyAsync(exons, p->d_final + L.out_exons, (size_t)p->final_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
-    PLAN_TRY(hipMemcpyAsync(steps, p->d_final + L.out_steps, (size_t)p->final_total, hipMemcpyDeviceToHost, st));
-  }
+  PLAN_TRY(drive_download(p->d_final, L, p->n_pat * sizeof *out, p->final_total, out, exons, steps, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   return PGPU_OK;
 }
@@ -929,8 +920,7 @@ extern "C" int pgpu_pairing_plan_run_units(pgpu_ctx* ctx, pgpu_pairing_plan* p, 
   p->unit_total = 0; p->n_units = 0; p->unit_ms = 0.f;
   lower(p, FINALS);
   if (const char* wrong = unit_params_wrong(*prm)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, wrong);
-  if (n_units > UNIT_MAX_COUNT || p->n_pat > UNIT_MAX_COUNT)
-    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 units or patterns in one call");
+  if (n_units > UNIT_MAX_COUNT || p->n_pat > UNIT_MAX_COUNT) return pgpu_ctx_fail(ctx, PGPU_EINVAL, UNIT_TOO_MANY);
   {
     const std::unique_ptr<uint8_t, void (*)(void*)> named((uint8_t*)calloc(p->n_pat ? p->n_pat : 1, 1), free);
     if (!named) return pgpu_ctx_fail(ctx, PGPU_ENOMEM, "no memory for the table of the patterns the units name");
@@ -941,10 +931,9 @@ extern "C" int pgpu_pairing_plan_run_units(pgpu_ctx* ctx, pgpu_pairing_plan* p, 
   if (p->n_pat == 0 || n_units == 0) return reached(p, UNITS);
   if (const int rc = still_owns(ctx, p, "finals")) return rc;
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
-  if (p->resident) p->d_unit = nullptr;                                        // taken anew: the pool may have moved
   const ProfRange range("units");
   const UnitLayout L = unit_layout(n_units, (size_t)p->final_total, pgpu_scan_tmp_bytes(n_units + 1));
-  PLAN_NEED(p->d_unit = plan_grow(p, p->d_unit, &p->unit_cap, L.total, L.total / 8, SLOT_UNITS));
+  PLAN_NEED(p->d_unit = stage_block(p, p->d_unit, &p->unit_cap, L.total, SLOT_UNITS));
   PLAN_TRY(plan_events(p, EV_UNITS, 2));
   const FinalLayout F = final_layout(p->n_pat, (size_t)p->cand_total, pgpu_scan_tmp_bytes(p->n_pat + 1));
   PLAN_TRY(hipMemcpyAsync(p->d_unit + L.q, q, n_units * sizeof *q, hipMemcpyHostToDevice, pgpu_ctx_stream(ctx)));
@@ -956,7 +945,7 @@ extern "C" int pgpu_pairing_plan_run_units(pgpu_ctx* ctx, pgpu_pairing_plan* p, 
   job.ev[0] = p->ev[EV_UNITS]; job.ev[1] = p->ev[EV_UNITS + 1];
   PLAN_TRY(pgpu_unit_drive(ctx, job));
   p->unit_total = job.total; p->n_units = n_units;
-  if (p->ev[EV_UNITS]) hipEventElapsedTime(&p->unit_ms, p->ev[EV_UNITS], p->ev[EV_UNITS + 1]);
+  elapsed_pairs(p, EV_UNITS, 1, &p->unit_ms);
   return reached(p, UNITS);
 }
 

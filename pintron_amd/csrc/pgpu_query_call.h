@@ -1,9 +1,11 @@
 // The host side of a query on the resident index, once: what the nine entries pgpu_index_find, pgpu_index_classify,
 // pgpu_index_small_exons, pgpu_index_refine_introns, pgpu_index_refine_chains, pgpu_index_clean_chains,
-// pgpu_index_gap_chains, pgpu_index_tail_chains and pgpu_index_small_chains share around their kernels.  An entry validates, lays out its device block, copies in, launches,
+// pgpu_index_gap_chains, pgpu_index_tail_chains and pgpu_index_small_chains, the index forms of the four device stages
+// (pgpu_index_candidates, pgpu_index_factorizations, pgpu_index_final_factorizations, pgpu_unit_records) and
+// pgpu_final_handoffs_probe share around their kernels.  An entry validates, lays out its device block, copies in, launches,
 // copies out and waits, as straight-line code; the QueryCall on its stack owns what has to be given back whichever way the
 // entry returns.  The five chained entries (one query = one list of exons, chained on the device) share more: the chained
-// path at the end.
+// path at the end.  What the stage drivers share is in pgpu_stage_drive.h.
 //
 // The contract of every entry (tests/test_gpu_query_calls.py): a refused call and an empty one leave the entry's
 // millisecond slot at 0; with pgpu_set_timing off the slot stays 0 and the answers are the same; a call that fails in
@@ -17,8 +19,7 @@
 #include <string.h>
 
 #include "pgpu_index.h"
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+#include "pgpu_layout.h"
 
 // a coordinate of a factor: -1 (unset) or an index into, or the length of, what it refers to (on the device too: the
 // factorization driver of pgpu_fact.hip asks it per query)
@@ -34,14 +35,14 @@ inline bool suffpref_ok(int32_t on_est, int32_t for_intron, int32_t on_gen) {
   return true;
 }
 
-// One call: the context's stream, the device blocks (`d`; `d2` for what can be sized only after a first phase), up to two
-// pairs of events, and the profiler range when the entry has a name for it.
+// One call: the context's stream, the device blocks (`d`; `d2` for what can be sized only after a first phase), up to seven
+// pairs of events (pgpu_index_final_factorizations takes them all), and the profiler range when the entry has a name for it.
 struct QueryCall {
   pgpu_ctx* const ctx;
   const hipStream_t st;
   uint8_t* d = nullptr;
   uint8_t* d2 = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[14] = {nullptr};
   bool failed = false;
   const bool range;
 
@@ -84,6 +85,11 @@ struct QueryCall {
     const hipError_t e_ = (expr);                       \
     if (e_ != hipSuccess) return call.fail(e_);         \
   } while (0)
+
+// pgpu_fact.hip: the job of the two index forms over the call's one block (the ESTs at 0, the n uploaded queries at `o_fq`, the
+// driver's block at `o_block`): uploads the candidate exons, takes the call's first eight events, hands ws_alloc over d2
+hipError_t pgpu_fact_index_job(QueryCall& call, const pgpu_index* idx, size_t o_fq, size_t o_block, const pgpu_factor* exons,
+                               size_t n_exons_total, size_t n, pgpu_fact_job& job);
 
 // ---- The chained path: pgpu_index_refine_chains, pgpu_index_clean_chains, pgpu_index_gap_chains,
 // pgpu_index_tail_chains and pgpu_index_small_chains.  Their query structs

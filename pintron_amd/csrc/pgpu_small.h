@@ -17,3 +17,4 @@ PGPU_TAIL_HD static inline bool small_query_ok(const pgpu_small_query& x, const 
 // config->min_intron_length may be any value (the prefix search compares it raw, the search between two exons takes
 // max(4, it)); only the reserved word is a rule
 static inline bool small_params_ok(const pgpu_small_params* p) { return p != nullptr && p->reserved == 0; }
+constexpr char SMALL_BAD_PARAMS[] = "bad small-chains parameters (reserved != 0)";

@@ -386,7 +386,7 @@ extern "C" int pgpu_index_small_chains(pgpu_ctx* ctx, const pgpu_index* idx, con
                 sizeof(pgpu_factor) == 16, "ABI layout");
   if (!ctx || !idx || !params) return PGPU_EINVAL;
   // before chained_begin, whose empty call writes the outputs: a refused call leaves them untouched
-  if (!small_params_ok(params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad small-chains parameters (reserved != 0)");
+  if (!small_params_ok(params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, SMALL_BAD_PARAMS);
   NamedExons named;
   const int begun = chained_begin(ctx, idx, ests, ests_len, exons, n_exons_total, q, n, out_exons, out_steps, out, "queries", named, 2);
   if (begun != CHAINED_GO) return begun;
@@ -407,9 +407,7 @@ extern "C" int pgpu_index_small_chains(pgpu_ctx* ctx, const pgpu_index* idx, con
   TRY_HIP(call.timing_events(1));
   TRY_HIP(chained_upload(call, L, ests, exons, q));
   TRY_HIP(call.record(0));
-  LcfIndexView ix = pgpu_index_lcf_view(idx);
-  if (!ix.focc || !ix.rmq) ix.first_bad = 0;      // an index without the derived tables: every prefix question is refused = 3
-  pgpu_small_launch(ix, cv, call.d, (const pgpu_factor*)(call.d + L.exons),
+  pgpu_small_launch(pgpu_index_small_view(idx), cv, call.d, (const pgpu_factor*)(call.d + L.exons),
                     (const pgpu_small_query*)(call.d + L.queries), (uint32_t)n, params->min_intron_length, waves,
                     (pgpu_factor*)(call.d + L.out_exons), call.d + L.out_bytes, (pgpu_small_result*)(call.d + L.results), call.st);
   TRY_HIP(call.record(1));

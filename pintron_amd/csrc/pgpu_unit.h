@@ -7,9 +7,11 @@
 #include <stdint.h>
 
 #include "../../include/pintron_gpu.h"
+#include "pgpu_layout.h"
 
 constexpr uint32_t UNIT_MAX_EXONS = 128;      // n_exons of a DONE pgpu_final_result
 constexpr size_t UNIT_MAX_COUNT = 0x7fffffffull;
+constexpr char UNIT_TOO_MANY[] = "more than 2^31 - 1 units or patterns in one call";
 
 // The parameters: null when they are good, else what is wrong with them.
 inline const char* unit_params_wrong(const pgpu_unit_params& p) {
@@ -22,7 +24,7 @@ inline const char* unit_params_wrong(const pgpu_unit_params& p) {
 // The units over n_pat patterns: null when they are good.  `named`: n_pat bytes, all 0 on entry; a pattern a unit names is
 // marked there.  No result is read.
 inline const char* unit_queries_wrong(const pgpu_unit_query* q, size_t n, size_t n_pat, uint8_t* named) {
-  if (n > UNIT_MAX_COUNT || n_pat > UNIT_MAX_COUNT) return "more than 2^31 - 1 units or patterns in one call";
+  if (n > UNIT_MAX_COUNT || n_pat > UNIT_MAX_COUNT) return UNIT_TOO_MANY;
   for (size_t i = 0; i < n; ++i) {
     const pgpu_unit_query& x = q[i];
     if (x.fwd >= n_pat) return "bad unit (fwd is no pattern)";
@@ -70,11 +72,10 @@ struct UnitLayout {
 };
 inline UnitLayout unit_layout(size_t n, size_t n_done_exons, size_t scan_tmp_bytes) {
   UnitLayout L;
-  size_t at = 0;
-  const auto take = [&at](size_t bytes) { const size_t o = at; at += ((bytes ? bytes : 1) + 255) & ~(size_t)255; return o; };
-  L.q = take(n * sizeof(pgpu_unit_query)); L.out = take(n * sizeof(pgpu_unit_result));
-  L.counts = take((n + 1) * sizeof(uint32_t)); L.first = take((n + 1) * sizeof(uint64_t)); L.scan_tmp = take(scan_tmp_bytes);
-  L.blob = take(unit_blob_bound(n, n_done_exons));
-  L.total = at;
+  BlockCarver c;
+  L.q = c.take(n * sizeof(pgpu_unit_query)); L.out = c.take(n * sizeof(pgpu_unit_result));
+  L.counts = c.take((n + 1) * sizeof(uint32_t)); L.first = c.take((n + 1) * sizeof(uint64_t)); L.scan_tmp = c.take(scan_tmp_bytes);
+  L.blob = c.take(unit_blob_bound(n, n_done_exons));
+  L.total = c.at;
   return L;
 }

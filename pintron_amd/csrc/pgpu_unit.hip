@@ -16,6 +16,7 @@
 
 #include "pgpu_internal.h"
 #include "pgpu_query_call.h"
+#include "pgpu_stage_drive.h"
 #include "pgpu_unit.h"
 
 namespace {
@@ -111,8 +112,6 @@ thread_local double t_unit_ms = 0.0;
 
 }  // namespace
 
-#define DRIVE(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t pgpu_unit_drive(pgpu_ctx* ctx, pgpu_unit_job& d) {
   const uint32_t n = d.n;
   d.total = 0;
@@ -127,17 +126,14 @@ hipError_t pgpu_unit_drive(pgpu_ctx* ctx, pgpu_unit_job& d) {
   const UnitGraphs g = { d.empty, d.recs, d.rec_first };
   const uint32_t pref_N = (uint32_t)d.params.pref_N_length, retain = d.params.retain_externals;
   const dim3 grid((n + 255) / 256), blk(256);
-  if (d.ev[0]) DRIVE(hipEventRecord(d.ev[0], st));
+  DRIVE(drive_record(d.ev, 0, st));
   hipLaunchKernelGGL(unit_kernel<false>, grid, blk, 0, st, uq, n, d.res, d.exons, d.n_exons_total, g, pref_N, retain, out, counts,
                      (const unsigned long long*)nullptr, (uint32_t*)nullptr);
-  DRIVE(hipMemsetAsync(counts + n, 0, sizeof(uint32_t), st));
-  pgpu_exclusive_scan_u32(counts, first, (size_t)n + 1, B + L.scan_tmp, st);
+  DRIVE(drive_scan(counts, first, n, B + L.scan_tmp, st));
   hipLaunchKernelGGL(unit_kernel<true>, grid, blk, 0, st, uq, n, d.res, d.exons, d.n_exons_total, g, pref_N, retain, out,
                      (uint32_t*)nullptr, first, (uint32_t*)(B + L.blob));
-  if (d.ev[1]) DRIVE(hipEventRecord(d.ev[1], st));
-  DRIVE(hipMemcpyAsync(&d.total, first + n, sizeof d.total, hipMemcpyDeviceToHost, st));
-  DRIVE(pgpu_ctx_wait(ctx));
-  return hipGetLastError();
+  DRIVE(drive_record(d.ev, 1, st));
+  return drive_total(ctx, first, n, &d.total);
 }
 
 extern "C" double pgpu_unit_records_kernel_ms(void) { return t_unit_ms; }
@@ -149,7 +145,7 @@ extern "C" int pgpu_unit_records(pgpu_ctx* ctx, const pgpu_final_result* res, si
   static_assert(sizeof(pgpu_unit_query) == 16 && sizeof(pgpu_unit_params) == 8 && sizeof(pgpu_unit_result) == 24, "ABI layout");
   if (!ctx || !params || !blob_len || (n && (!q || !out)) || (n_pat && !res) || (n_exons_total && !exons) || (blob_cap && !blob))
     return PGPU_EINVAL;
-  if (n > UNIT_MAX_COUNT || n_pat > UNIT_MAX_COUNT) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 units or patterns in one call");
+  if (n > UNIT_MAX_COUNT || n_pat > UNIT_MAX_COUNT) return pgpu_ctx_fail(ctx, PGPU_EINVAL, UNIT_TOO_MANY);
   if (const char* wrong = unit_params_wrong(*params)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, wrong);
   if (const char* wrong = unit_finals_wrong(res, n_pat, n_exons_total)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, wrong);
   NamedExons named;                                    // here: which patterns a unit has named already

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../pintron_amd/csrc/pgpu_final.h"
+#include "../../pintron_amd/csrc/pgpu_unit.h"
 
 static int failures = 0;
 #define EXPECT(cond) do { if (!(cond)) { printf("line %d: %s\n", __LINE__, #cond); ++failures; } } while (0)
@@ -113,6 +114,43 @@ int main() {
     for (int k = 0; k < 16; ++k) EXPECT(at[k] % 256 == 0 && at[k] + len[k] <= at[k + 1]);
     // the placeholder of the last EST and its list in small's output lie inside their arrays
     EXPECT((e + n - 1 + 1) * 16 <= L.ex_tout - L.ex_tin && (2 * (e + n - 1) + 2) * 16 <= L.tsteps - L.ex_sout);
+  }
+  // ---- the block carver (pgpu_layout.h) under the three stage layouts: no offset and no total moves.  Per row: n,
+  // n_exons_total (for unit_layout: n_done_exons), then the 22 offsets of fact_layout, the 17 of final_layout and the 7 of
+  // unit_layout in the order of their structs, at scan_tmp_bytes = 24; the literals were printed by the layouts as they
+  // stood before the carver.
+  {
+    static const struct { size_t n, e, at[46]; } rows[] = {
+    { 0, 0, { 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 4352, 4608, 4864, 5120, 5376, 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 0, 256, 512, 768, 1024, 1280, 1536 } },
+    { 0, 1, { 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 4352, 4608, 4864, 5120, 5376, 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 0, 256, 512, 768, 1024, 1280, 1536 } },
+    { 0, 300, { 0, 4864, 9728, 14592, 19456, 24320, 24832, 25344, 25856, 26112, 26368, 26624, 26880, 27136, 27392, 27648, 27904, 28160, 28416, 28672, 33536, 34048, 0, 4864, 9728, 14592, 24320, 24832, 25600, 25856, 26112, 26368, 26624, 26880, 27136, 27392, 27648, 37376, 38144, 0, 256, 512, 768, 1024, 1280, 6144 } },
+    { 1, 0, { 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 4352, 4608, 4864, 5120, 5376, 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 0, 256, 512, 768, 1024, 1280, 1536 } },
+    { 1, 1, { 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 4352, 4608, 4864, 5120, 5376, 0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2304, 2560, 2816, 3072, 3328, 3584, 3840, 4096, 0, 256, 512, 768, 1024, 1280, 1536 } },
+    { 1, 300, { 0, 4864, 9728, 14592, 19456, 24320, 24832, 25344, 25856, 26112, 26368, 26624, 26880, 27136, 27392, 27648, 27904, 28160, 28416, 28672, 33536, 34048, 0, 4864, 9728, 14592, 24320, 24832, 25600, 25856, 26112, 26368, 26624, 26880, 27136, 27392, 27648, 37376, 38144, 0, 256, 512, 768, 1024, 1280, 6144 } },
+    { 255, 0, { 0, 4096, 8192, 12288, 16384, 20480, 20736, 20992, 21248, 29440, 33536, 39680, 43776, 54016, 58112, 62208, 62464, 63488, 65536, 65792, 66048, 66304, 0, 4096, 8192, 12288, 20480, 20736, 21248, 29440, 33536, 41728, 47872, 56064, 57088, 59136, 59392, 59648, 59904, 0, 4096, 10240, 11264, 13312, 13568, 16640 } },
+    { 255, 1, { 0, 4096, 8192, 12288, 16384, 20480, 20736, 20992, 21248, 29440, 33536, 39680, 43776, 54016, 58112, 62208, 62464, 63488, 65536, 65792, 66048, 66304, 0, 4096, 8192, 12288, 20480, 20736, 21248, 29440, 33536, 41728, 47872, 56064, 57088, 59136, 59392, 59648, 59904, 0, 4096, 10240, 11264, 13312, 13568, 16896 } },
+    { 255, 300, { 0, 8960, 17920, 26880, 35840, 44800, 45568, 46336, 47104, 55296, 59392, 65536, 69632, 79872, 83968, 88064, 88320, 89344, 91392, 91648, 96512, 97024, 0, 8960, 17920, 26880, 44800, 45568, 46848, 55040, 59136, 67328, 73472, 81664, 82688, 84736, 84992, 94720, 95488, 0, 4096, 10240, 11264, 13312, 13568, 21504 } },
+    { 256, 0, { 0, 4096, 8192, 12288, 16384, 20480, 20736, 20992, 21248, 29440, 33536, 39680, 43776, 54016, 58112, 62208, 62464, 63744, 66048, 66304, 66560, 66816, 0, 4096, 8192, 12288, 20480, 20736, 21248, 29440, 33536, 41728, 47872, 56064, 57344, 59648, 59904, 60160, 60416, 0, 4096, 10240, 11520, 13824, 14080, 17152 } },
+    { 256, 1, { 0, 4352, 8704, 13056, 17408, 21760, 22272, 22784, 23296, 31488, 35584, 41728, 45824, 56064, 60160, 64256, 64512, 65792, 68096, 68352, 68608, 68864, 0, 4352, 8704, 13056, 21504, 22016, 22784, 30976, 35072, 43264, 49408, 57600, 58880, 61184, 61440, 61696, 61952, 0, 4096, 10240, 11520, 13824, 14080, 17408 } },
+    { 256, 300, { 0, 8960, 17920, 26880, 35840, 44800, 45568, 46336, 47104, 55296, 59392, 65536, 69632, 79872, 83968, 88064, 88320, 89600, 91904, 92160, 97024, 97536, 0, 8960, 17920, 26880, 44800, 45568, 46848, 55040, 59136, 67328, 73472, 81664, 82944, 85248, 85504, 95232, 96000, 0, 4096, 10240, 11520, 13824, 14080, 22016 } },
+    { 257, 0, { 0, 4352, 8704, 13056, 17408, 21760, 22272, 22784, 23296, 31744, 36096, 42496, 46848, 57344, 61696, 66048, 66304, 67584, 69888, 70144, 70400, 70656, 0, 4352, 8704, 13056, 21504, 22016, 22784, 31232, 35584, 44032, 50432, 58880, 60160, 62464, 62720, 62976, 63232, 0, 4352, 10752, 12032, 14336, 14592, 17920 } },
+    { 257, 1, { 0, 4352, 8704, 13056, 17408, 21760, 22272, 22784, 23296, 31744, 36096, 42496, 46848, 57344, 61696, 66048, 66304, 67584, 69888, 70144, 70400, 70656, 0, 4352, 8704, 13056, 21504, 22016, 22784, 31232, 35584, 44032, 50432, 58880, 60160, 62464, 62720, 62976, 63232, 0, 4352, 10752, 12032, 14336, 14592, 17920 } },
+    { 257, 300, { 0, 8960, 17920, 26880, 35840, 44800, 45568, 46336, 47104, 55552, 59904, 66304, 70656, 81152, 85504, 89856, 90112, 91392, 93696, 93952, 98816, 99328, 0, 8960, 17920, 26880, 44800, 45568, 46848, 55296, 59648, 68096, 74496, 82944, 84224, 86528, 86784, 96512, 97280, 0, 4352, 10752, 12032, 14336, 14592, 22528 } },
+    };
+    EXPECT(sizeof rows / sizeof rows[0] == 15);
+    for (const auto& r : rows) {
+      const FactLayout A = fact_layout(r.n, r.e, 24);
+      const FinalLayout B = final_layout(r.n, r.e, 24);
+      const UnitLayout C = unit_layout(r.n, r.e, 24);
+      const size_t got[46] = { A.ex_in, A.ex_clean, A.ex_gaps, A.ex_kept, A.ex_refined, A.marks, A.gsteps, A.rsteps, A.cq, A.cr, A.gq,
+                               A.gr, A.rq, A.rr, A.res, A.need, A.counts, A.first, A.scan_tmp, A.out_exons, A.out_steps, A.total,
+                               B.ex_tin, B.ex_tout, B.ex_sin, B.ex_sout, B.tsteps, B.ssteps, B.tq, B.tr, B.sq, B.sr, B.res, B.counts,
+                               B.first, B.scan_tmp, B.out_exons, B.out_steps, B.total,
+                               C.q, C.out, C.counts, C.first, C.scan_tmp, C.blob, C.total };
+      for (int k = 0; k < 46; ++k) EXPECT(got[k] == r.at[k]);
+    }
+    BlockCarver c;
+    EXPECT(c.take(0) == 0 && c.take(1) == 256 && c.take(256) == 512 && c.take(257) == 768 && c.at == 1280);
   }
   if (!failures) printf("ok\n");
   return failures != 0;

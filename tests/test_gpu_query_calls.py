@@ -2,18 +2,24 @@
 (pintron_amd/csrc/pgpu_query_call.h), entry by entry on one sequence of 700 bases with two or three queries each:
 the millisecond slot is set with timing on and 0.0 without it, with the same answers; a call refused with PGPU_EINVAL
 resets the slot and leaves its message; the context answers the same afterwards; an empty call is PGPU_OK with the slot
-at 0.  For pgpu_index_find also the PGPU_ENOSPC round and a second context on the same index.  The answers are held
-against the CPU restatements (bytes.find, tests/small_exon_lib.py, tests/refine_lib.py, tests/chain_lib.py,
-tests/clean_lib.py), never against the library alone; the messages are the literal texts of the source."""
+at 0.  The same for the index forms of the four device stages (pgpu_index_candidates, pgpu_index_factorizations,
+pgpu_index_final_factorizations, pgpu_unit_records).  For pgpu_index_find also the PGPU_ENOSPC round and a second context
+on the same index.  The answers are held against the CPU restatements (bytes.find, tests/small_exon_lib.py,
+tests/refine_lib.py, tests/chain_lib.py, tests/clean_lib.py, tests/cand_lib.py, tests/fact_lib.py, tests/final_lib.py,
+tests/unit_lib.py), never against the library alone; the messages are the literal texts of the source."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import cand_lib as DL
 import chain_lib as CL
 import clean_lib as KL
+import fact_lib as FA
+import final_lib as FL
 import refine_lib as RL
 import small_exon_lib as SL
+import unit_lib as UL
 
 pytestmark = pytest.mark.gpu
 
@@ -26,6 +32,10 @@ MESSAGES = {
                      "is not in front of its acceptor, or a coordinate outside what it indexes)",
     "clean_chains": "bad clean query (a range past its buffer, an empty EST, reserved != 0, no exon, an exon two queries share, a "
                     "coordinate outside what it indexes, or an end exon that begins in front of or ends behind its sequence)",
+    "candidates": "bad candidate parameters (min_factor_len 0 or above 2^24)",
+    "factorizations": "bad factorization query (a range past its buffer, an empty EST, reserved != 0, or an exon two queries share)",
+    "final_factorizations": "bad final query (a range past its buffer, an empty EST, reserved != 0, or an exon two queries share)",
+    "unit_records": "bad unit (flag bits beyond 0-1)",
 }
 
 
@@ -198,12 +208,89 @@ def world(O):
     e.kq = kq
     e.ms = lambda: (idx.clean_chains_kernel_ms(),)
 
+    # ---- the index forms of the four device stages, two queries each: the chain's two exons, and a single short exon (the
+    # first thirty bases of the chain's first one).  Every kernel of a stage runs once; in the factorizations the chain ends
+    # EMPTY at the cleaning and the short exon is DONE, so the compact answer has one exon and is copied out.
+    chain_ex = [tuple(int(v) for v in x) for x in exons]
+    short_ex = [(chain_ex[0][0], chain_ex[0][0] + 29, chain_ex[0][2], chain_ex[0][2] + 29)]
+    lo = chain_ex[0][0]
+    est2, est1 = est[lo:chain_ex[-1][1] + 1], est[lo:lo + 30]            # the stretches of the EST the two lists cover
+    chain2, short1 = [(a - lo, b - lo, g0, g1) for a, b, g0, g1 in chain_ex], [(0, 29) + short_ex[0][2:]]
+
+    # candidates: one record per list, a pairing per exon
+    recs = [DL.record(*DL.chain([(a, g0, min(b - a, g1 - g0) + 1) for a, b, g0, g1 in ex])) for ex in (chain_ex, short_ex)]
+    dblob, dfirst = DL.batch(recs)
+    dres, dex = DL.expect_arrays([DL.candidate(r, gen, 15, 40) for r in recs])
+
+    def candidates(n, L=15):
+        rc, res, ex, total = idx.candidates_raw(dblob, dfirst, n, L, 40, len(dex))
+        return rc, res.tobytes() + ex[:total].tobytes()
+    e = entries["candidates"] = Entry()
+    e.good = lambda: candidates(len(recs))
+    e.want = dres.tobytes() + dex.tobytes()
+    e.bad = lambda: candidates(len(recs), L=0)[0]
+    e.empty = lambda: candidates(0)[0]
+    e.ms = lambda: (idx.candidates_kernel_ms(),)
+
+    # factorizations
+    aests, aexons, aq = FA.batch_arrays([(est2, chain2), (est1, short1)])
+    awant = FA.expect_arrays([FA.factorization(DL.ONE, x, gen, ex) for x, ex in ((est2, chain2), (est1, short1))])
+    assert [int(o) for o in awant[0]["outcome"]] == [FA.EMPTY, FA.DONE] and len(awant[1]) == 1
+    abad = aq.copy()
+    abad["reserved"][1] = 1
+
+    def factorizations(q, n):
+        rc, res, ex, st, total = idx.factorizations_raw(aests, aexons, q, n, capi.FactParams(*FA.DEFAULTS), len(aexons))
+        return rc, res.tobytes() + ex[:total].tobytes() + st[:total].tobytes()
+    e = entries["factorizations"] = Entry()
+    e.good = lambda: factorizations(aq, len(aq))
+    e.want = b"".join(a.tobytes() for a in awant)
+    e.bad = lambda: factorizations(abad, len(abad))[0]
+    e.empty = lambda: factorizations(aq, 0)[0]
+    e.ms = lambda: (idx.factorizations_kernel_ms(),)
+
+    # final factorizations: the ESTs are their own originals
+    nests, nexons, nq = FL.batch_arrays([(est2, est2, chain2), (est1, est1, short1)])
+    nwant = FL.expect_arrays([FL.final(DL.ONE, x, x, gen, ex, FA.DEFAULTS, 40) for x, ex in ((est2, chain2), (est1, short1))])
+    assert [int(o) for o in nwant[0]["outcome"]] == [FL.EMPTY, FL.DONE] and len(nwant[1]) == 1
+    nbad = nq.copy()
+    nbad["reserved"][1] = 1
+
+    def finals(q, n):
+        rc, res, ex, st, total = idx.final_factorizations_raw(nests, nexons, q, n, capi.FactParams(*FA.DEFAULTS), capi.SmallParams(40, 0),
+                                                              2 * len(nexons))
+        return rc, res.tobytes() + ex[:total].tobytes() + st[:total].tobytes()
+    e = entries["final_factorizations"] = Entry()
+    e.good = lambda: finals(nq, len(nq))
+    e.want = b"".join(a.tobytes() for a in nwant)
+    e.bad = lambda: finals(nbad, len(nbad))[0]
+    e.empty = lambda: finals(nq, 0)[0]
+    e.ms = lambda: (idx.final_factorizations_kernel_ms(),)
+
+    # unit records: an aligned pattern with its sibling, and one whose only pattern has a single short exon
+    ures, uexons, uempty, uq = UL.batch([dict(fwd=UL.aligned(), rev=UL.aligned((31, 32, 33, 34)), flags=0, est_index=7),
+                                         dict(fwd=UL.aligned((2,)), rev=None, flags=0, est_index=9)])
+    uout, ublob = UL.units(ures, uexons, uempty, uq)
+    ubad = uq.copy()
+    ubad["flags"][1] = 4
+
+    def units(q, n):
+        rc, out, blob, total = capi.unit_records_raw(ctx, ures, uexons, uempty, q, n, capi.unit_params(0, 1), len(ublob))
+        return rc, out.tobytes() + blob[:total].tobytes()
+    e = entries["unit_records"] = Entry()
+    e.good = lambda: units(uq, len(uq))
+    e.want = uout.tobytes() + ublob
+    e.bad = lambda: units(ubad, len(ubad))[0]
+    e.empty = lambda: units(uq, 0)[0]
+    e.ms = lambda: (ctx.L.pgpu_unit_records_kernel_ms(),)
+
     yield capi, ctx, idx, gen, entries
     idx.close()
     ctx.close()
 
 
-@pytest.mark.parametrize("name", ["find", "small_exons", "refine_introns", "refine_chains", "clean_chains"])
+@pytest.mark.parametrize("name", ["find", "small_exons", "refine_introns", "refine_chains", "clean_chains", "candidates",
+                                  "factorizations", "final_factorizations", "unit_records"])
 def test_the_contract_of_a_timed_entry(world, name):
     capi, ctx, idx, gen, entries = world
     e = entries[name]
