@@ -1088,6 +1088,91 @@ int pgpu_pairing_plan_fetch_units(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_u
 /* HIP-event time of the last run_units (count + scan + write); 0 without timing */
 double pgpu_pairing_plan_units_ms(const pgpu_pairing_plan* plan);
 
+/* ------------------------------------------------------------------------------------------ */
+/* texts -- from a unit's group in the packed records to est-fact's two text files: the lines   */
+/* of raw-multifasta-out.txt (write_multifasta_output, src/io-multifasta.c:187-229; on the host */
+/* side ef_raw_text_from_records, pintron_amd/host/ef_records.c) and the entry of               */
+/* processed-ests.txt (ef_write_single_est_info).  Everything but a few decimal numbers is a   */
+/* substring of a sequence that lies in HBM.  Nothing in the library calls these entries yet.   */
+/* ------------------------------------------------------------------------------------------ */
+#define PGPU_TEXT_MAX_UNIT_BYTES (1u << 24)
+#define PGPU_TEXT_NONE 0u   /* the unit is not ALIGNED: no bytes in either blob */
+#define PGPU_TEXT_DONE 1u   /* both texts are written */
+#define PGPU_TEXT_HOST 2u   /* raw(u) or pests(u) is longer than PGPU_TEXT_MAX_UNIT_BYTES: no bytes, the caller prints this EST */
+typedef struct {
+  uint64_t raw_first, pests_first;   /* DONE only, else 0: where the unit's texts begin in the two blobs */
+  uint32_t raw_bytes, pests_bytes;   /* DONE only, else 0 */
+  uint8_t  verdict;                  /* PGPU_TEXT_* */
+  uint8_t  reserved[7];
+} pgpu_text_result;         /* 32 bytes */
+
+/* The rule.  For an ALIGNED unit u: H is its header bytes (ef_seq.id, the same for both strands: ef_copy_and_reverse), S
+ * the original sequence of the pattern that decided (pgpu_unit_result.pattern), sl bytes, G the original genomic sequence
+ * (ef_seq.original_seq, N prefix included), gl bytes, and the group is blob[first_byte .. first_byte + n_bytes).
+ *    pests(u) = ">" H "\n" S "\n"
+ *    raw(u)   = for each factorization of the group, in order:
+ *                 ">" H "\n#polya=" d(polya) "\n#polyad=" d(polyad) "\n", then per exon
+ *                 d(est_start) " " d(est_end) " " d(gen_start) " " d(gen_end) " " E " " X "\n"
+ *  - d is printf("%d") of the stored value: u8 for the flags, i32 for the four numbers, "-" for negatives,
+ *    "-2147483648" for INT_MIN.
+ *  - E is the stretch of S: with a = est_start and b = est_end as 64-bit integers it is empty unless
+ *    a >= 1 && a <= sl + 1 && b >= a; otherwise it is S[a-1 .. a-1+n) with n = min(b + 1 - a, sl - (a - 1)).
+ *    X is the same rule on G with gl.  This is ef_raw_text_from_records' rule stated in 64 bits, so that no input is
+ *    undefined; for the records the chain makes it equals ef_write_multifasta_output.
+ *  - A group of 8 bytes (n_factorizations == 0) has an empty raw and a full pests.  Headers are copied as they are,
+ *    whatever bytes they hold.
+ *  - Per unit one pgpu_text_result: NONE for a unit that is not ALIGNED; HOST when raw(u) or pests(u) is longer than
+ *    PGPU_TEXT_MAX_UNIT_BYTES (the count formed in 64 bits); DONE otherwise.  Both blobs are compact and in UNIT order: a
+ *    call whose units are all settled produces est-fact's two files for those ESTs byte for byte. */
+
+/* The original genomic sequence in HBM (len bytes, copied).  len == 0 or a null pointer: PGPU_EINVAL. */
+typedef struct pgpu_text_source pgpu_text_source;
+int pgpu_text_source_create(pgpu_ctx* ctx, const char* genomic_original, size_t len, pgpu_text_source** src);
+int pgpu_text_source_destroy(pgpu_ctx* ctx, pgpu_text_source* src);
+
+/* The form without a plan: fetched or host-made records, no index, any well-formed group (several factorizations too: the
+ * device twin of ef_raw_text_from_records).  units: n results of the unit stage; blob: the groups they name; headers:
+ * headers_len bytes, hdr_first: n + 1 offsets, unit i's header is headers[hdr_first[i] .. hdr_first[i+1]); seqs: seqs_len
+ * bytes, seq_first: n_pat + 1 offsets, one sequence per pattern; genomic: genomic_len bytes; out: n results; raw / pests:
+ * raw_cap / pests_cap bytes; *raw_len, *pests_len: bytes written.  One upload, one download; synchronous.
+ *  - PGPU_EINVAL for the whole call, for structure only: a null pointer (no message); offsets that do not ascend or that
+ *    pass their length; a verdict above 2; an ALIGNED unit whose pattern >= n_pat, whose first_byte + n_bytes > blob_len,
+ *    whose first_byte or n_bytes is no multiple of 4, or whose factorization headers do not add up to exactly n_bytes;
+ *    more than 2^31 - 1 units or patterns.
+ *  - PGPU_ENOSPC, with both needed sizes in *raw_len and *pests_len and nothing written to out, raw or pests, when a cap
+ *    is too small.
+ *  - n == 0 is PGPU_OK (both lengths 0). */
+int pgpu_unit_texts(pgpu_ctx* ctx, const pgpu_unit_result* units, size_t n, const void* blob, size_t blob_len,
+                    const char* headers, size_t headers_len, const uint64_t* hdr_first,
+                    const char* seqs, size_t seqs_len, const uint64_t* seq_first, size_t n_pat,
+                    const char* genomic, size_t genomic_len, pgpu_text_result* out,
+                    void* raw, size_t raw_cap, size_t* raw_len, void* pests, size_t pests_cap, size_t* pests_len);
+/* HIP-event time of the kernels of the calling thread's last pgpu_unit_texts on a context with timing on (as
+ * pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_unit_texts_kernel_ms(void);
+
+/* Plan form: the units and the blob of the last pgpu_pairing_plan_run_units, where they lie; the sequences are the plan's
+ * originals where a pattern has one, else its own bytes, their lengths from the pattern offsets; G is `src`.  headers /
+ * hdr_first: n_units + 1 offsets for the units of that run_units, uploaded at every call.  The seventh stage of a plan:
+ * units and finals stay fetchable and unchanged; a run of any earlier stage takes the texts with it.
+ * PGPU_EINVAL (with a message): bad header offsets; a source made on another context; no run_units since the last run of
+ * an earlier stage; the results of a resident plan were overwritten by the run of another one; fetch before the run.  A
+ * null pointer is a bare PGPU_EINVAL (headers may be null when headers_len == 0, hdr_first when the run had no units).  An empty plan or a run of zero units is
+ * PGPU_OK.  A rerun gives the same bytes.  The buffers come from where the MEG stage's do, in slots of the stage's own.
+ * The one host wait of the call is for the two byte totals that size the blobs: the write pass is still queued when the
+ * call returns, and fetch_texts (or texts_ms) waits for it. */
+int pgpu_pairing_plan_run_texts(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_text_source* src, const char* headers,
+                                size_t headers_len, const uint64_t* hdr_first);
+/* bytes of a blob of the last run_texts: which == 0 raw, 1 pests, anything else 0 */
+uint64_t pgpu_pairing_plan_text_bytes(const pgpu_pairing_plan* plan, int which);
+/* out: as many results as the last run_units had units; PGPU_ENOSPC when a cap is smaller than its text_bytes */
+int pgpu_pairing_plan_fetch_texts(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_text_result* out, void* raw, size_t raw_cap,
+                                  void* pests, size_t pests_cap);
+/* HIP-event time of the last run_texts (count + scans + write; waits for the write pass); 0 without timing */
+double pgpu_pairing_plan_texts_ms(pgpu_pairing_plan* plan);
+/* the write pass alone, the same way */
+double pgpu_pairing_plan_texts_write_ms(pgpu_pairing_plan* plan);
+
 /* page-locked host memory for the buffers handed to the fetch calls (a pageable destination
  * makes the runtime stage the copy); plain malloc'ed memory works too, slower */
 int pgpu_host_alloc(pgpu_ctx* ctx, size_t bytes, void** out);

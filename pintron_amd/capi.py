@@ -171,6 +171,11 @@ class UnitResult(C.Structure):     # pgpu_unit_result
                 ("pattern", C.c_uint32), ("first_byte", C.c_uint64), ("n_bytes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TextResult(C.Structure):     # pgpu_text_result
+    _fields_ = [("raw_first", C.c_uint64), ("pests_first", C.c_uint64), ("raw_bytes", C.c_uint32), ("pests_bytes", C.c_uint32),
+                ("verdict", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -221,6 +226,10 @@ FINAL_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("f
 FINAL_QUERY_DTYPE = TAIL_QUERY_DTYPE
 UNIT_NO_SIBLING, UNIT_FWD_SUFF_POLYA, UNIT_REV_SUFF_POLYA = 0xffffffff, 1, 2
 UNIT_HOST, UNIT_UNALIGNED, UNIT_ALIGNED = range(3)
+TEXT_NONE, TEXT_DONE, TEXT_HOST = range(3)
+TEXT_MAX_UNIT_BYTES = 1 << 24
+TEXT_RESULT_DTYPE = [("raw_first", "<u8"), ("pests_first", "<u8"), ("raw_bytes", "<u4"), ("pests_bytes", "<u4"), ("verdict", "u1"),
+                     ("reserved", "u1", (7,))]
 UNIT_QUERY_DTYPE = [("est_index", "<u4"), ("fwd", "<u4"), ("rev", "<u4"), ("flags", "<u4")]
 UNIT_RESULT_DTYPE = [("verdict", "u1"), ("strand", "u1"), ("reason", "u1"), ("n_factorizations", "u1"), ("pattern", "<u4"),
                      ("first_byte", "<u8"), ("n_bytes", "<u4"), ("reserved", "<u4")]
@@ -243,6 +252,7 @@ assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
 assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
 assert C.sizeof(FinalResult) == 32 and C.sizeof(FinalQuery) == 32
 assert C.sizeof(UnitQuery) == 16 and C.sizeof(UnitParams) == 8 and C.sizeof(UnitResult) == 24
+assert C.sizeof(TextResult) == 32
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -270,6 +280,9 @@ EXPORTS = [
     "pgpu_index_final_factorizations_kernel_ms",
     "pgpu_unit_records", "pgpu_unit_records_kernel_ms", "pgpu_pairing_plan_run_units", "pgpu_pairing_plan_unit_bytes",
     "pgpu_pairing_plan_fetch_units", "pgpu_pairing_plan_units_ms",
+    "pgpu_text_source_create", "pgpu_text_source_destroy", "pgpu_unit_texts", "pgpu_unit_texts_kernel_ms",
+    "pgpu_pairing_plan_run_texts", "pgpu_pairing_plan_text_bytes", "pgpu_pairing_plan_fetch_texts", "pgpu_pairing_plan_texts_ms",
+    "pgpu_pairing_plan_texts_write_ms",
     "pgpu_comm_unique_id", "pgpu_comm_init", "pgpu_gather", "pgpu_allgather", "pgpu_comm_destroy",
     "pgpu_range_push", "pgpu_range_pop", "pgpu_build_info",
     "pgpu_dp_plan_create", "pgpu_dp_plan_create_parts", "pgpu_dp_plan_launch", "pgpu_dp_plan_sync",
@@ -399,6 +412,20 @@ def lib():
         L.pgpu_pairing_plan_fetch_units.argtypes = [vp, vp, C.POINTER(UnitResult), vp, sz]
         L.pgpu_pairing_plan_units_ms.argtypes = [vp]
         L.pgpu_pairing_plan_units_ms.restype = C.c_double
+        L.pgpu_text_source_create.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp)]
+        L.pgpu_text_source_destroy.argtypes = [vp, vp]
+        L.pgpu_unit_texts.argtypes = [vp, C.POINTER(UnitResult), sz, vp, sz, vp, sz, C.POINTER(u64), vp, sz, C.POINTER(u64), sz,
+                                      vp, sz, C.POINTER(TextResult), vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
+        L.pgpu_unit_texts_kernel_ms.argtypes = []
+        L.pgpu_unit_texts_kernel_ms.restype = C.c_double
+        L.pgpu_pairing_plan_run_texts.argtypes = [vp, vp, vp, vp, sz, C.POINTER(u64)]
+        L.pgpu_pairing_plan_text_bytes.argtypes = [vp, C.c_int]
+        L.pgpu_pairing_plan_text_bytes.restype = u64
+        L.pgpu_pairing_plan_fetch_texts.argtypes = [vp, vp, C.POINTER(TextResult), vp, sz, vp, sz]
+        L.pgpu_pairing_plan_texts_ms.argtypes = [vp]
+        L.pgpu_pairing_plan_texts_ms.restype = C.c_double
+        L.pgpu_pairing_plan_texts_write_ms.argtypes = [vp]
+        L.pgpu_pairing_plan_texts_write_ms.restype = C.c_double
         L.pgpu_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.pgpu_host_free.argtypes = [vp, vp]
         L.pgpu_comm_unique_id.argtypes = [vp, vp]
@@ -858,6 +885,61 @@ def unit_records(ctx, res, exons, empty_graph, queries, pref_N_length=0, retain_
     return out, blob[:total].tobytes()
 
 
+def _offsets(parts):
+    """the bytes of `parts` joined, and their len(parts) + 1 offsets as a numpy uint64 array"""
+    import numpy as np
+    first = np.zeros(len(parts) + 1, dtype=np.uint64)
+    if parts:
+        np.cumsum([len(x) for x in parts], out=first[1:])
+    return b"".join(parts), first
+
+
+def unit_texts_raw(ctx, units, n, blob, headers, hdr_first, seqs, seq_first, n_pat, genomic, raw_cap, pests_cap,
+                   blob_len=None, headers_len=None, seqs_len=None):
+    """One pgpu_unit_texts call as it is: `units` a numpy array of UNIT_RESULT_DTYPE, `blob`, `headers`, `seqs`, `genomic`
+    bytes, `hdr_first` and `seq_first` numpy uint64 arrays.  Returns (rc, results as a numpy array of TEXT_RESULT_DTYPE, raw
+    and pests as numpy uint8 arrays of their caps, raw_len, pests_len)."""
+    import numpy as np
+    out = np.zeros(min(n, len(units)), dtype=np.dtype(TEXT_RESULT_DTYPE))
+    raw, pests = np.zeros(raw_cap, dtype=np.uint8), np.zeros(pests_cap, dtype=np.uint8)
+    raw_len, pests_len = C.c_size_t(0), C.c_size_t(0)
+    b = lambda x: C.cast(C.c_char_p(x), C.c_void_p)
+    rc = ctx.L.pgpu_unit_texts(
+        ctx.h, units.ctypes.data_as(C.POINTER(UnitResult)), n, b(blob), len(blob) if blob_len is None else blob_len,
+        b(headers), len(headers) if headers_len is None else headers_len, hdr_first.ctypes.data_as(C.POINTER(C.c_uint64)),
+        b(seqs), len(seqs) if seqs_len is None else seqs_len, seq_first.ctypes.data_as(C.POINTER(C.c_uint64)), n_pat,
+        b(genomic), len(genomic), out.ctypes.data_as(C.POINTER(TextResult)),
+        raw.ctypes.data_as(C.c_void_p), raw_cap, C.byref(raw_len), pests.ctypes.data_as(C.c_void_p), pests_cap, C.byref(pests_len))
+    return rc, out, raw, pests, raw_len.value, pests_len.value
+
+
+def unit_texts(ctx, units, blob, headers, seqs, genomic):
+    """The two texts of every ALIGNED unit: `units` a numpy array of UNIT_RESULT_DTYPE over `blob`, `headers` one bytes per
+    unit, `seqs` one bytes per pattern, `genomic` the original genomic sequence -> (results as a numpy array of
+    TEXT_RESULT_DTYPE, raw as bytes, pests as bytes).  Two calls: the first one asks for the sizes."""
+    hb, hf = _offsets(headers)
+    sb, sf = _offsets(seqs)
+    args = (ctx, units, len(units), blob, hb, hf, sb, sf, len(seqs), genomic)
+    rc, out, raw, pests, raw_len, pests_len = unit_texts_raw(*args, 0, 0)
+    if rc == PGPU_ENOSPC:
+        rc, out, raw, pests, raw_len, pests_len = unit_texts_raw(*args, raw_len, pests_len)
+    ctx.check(rc)
+    return out, raw[:raw_len].tobytes(), pests[:pests_len].tobytes()
+
+
+class TextSource:
+    """The original genomic sequence in HBM, for PairingPlan.run_texts"""
+
+    def __init__(self, ctx, genomic: bytes):
+        self.ctx, self.h = ctx, C.c_void_p()
+        ctx.check(ctx.L.pgpu_text_source_create(ctx.h, genomic, len(genomic), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.ctx.L.pgpu_text_source_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+
 class MegParams(C.Structure):       # pgpu_meg_params; defaults = src/options.ggo:94-370
     _fields_ = [("min_factor_len", C.c_uint32), ("min_intron_length", C.c_int32), ("max_intron_length", C.c_int32),
                 ("max_pairings_in_MEG", C.c_uint32), ("max_prefix_discarded_rate", C.c_double),
@@ -1066,6 +1148,47 @@ class PairingPlan:
     def units_ms(self):
         """HIP-event time of the last run_units (count + scan + write)"""
         return self.ctx.L.pgpu_pairing_plan_units_ms(self.h)
+
+    def run_texts_raw(self, source, headers, headers_len, hdr_first):
+        """source: a TextSource (or None), headers: bytes (or None), hdr_first: a numpy uint64 array (or None)"""
+        return self.ctx.L.pgpu_pairing_plan_run_texts(
+            self.ctx.h, self.h, None if source is None else source.h,
+            None if headers is None else C.cast(C.c_char_p(headers), C.c_void_p), headers_len,
+            None if hdr_first is None else hdr_first.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def run_texts(self, source, headers):
+        """the units of the last run_units to est-fact's two texts, where they lie; headers: one bytes per unit
+        -> (bytes of raw, bytes of pests)"""
+        hb, hf = _offsets(headers)
+        self.ctx.check(self.run_texts_raw(source, hb, len(hb), hf))
+        return self.text_bytes(0), self.text_bytes(1)
+
+    def text_bytes(self, which):
+        return self.ctx.L.pgpu_pairing_plan_text_bytes(self.h, which)
+
+    def fetch_texts_raw(self, n_units, raw_cap=None, pests_cap=None):
+        """(rc, results as a numpy array of TEXT_RESULT_DTYPE, one per unit; raw and pests as numpy uint8 arrays)"""
+        import numpy as np
+        rn = self.text_bytes(0) if raw_cap is None else raw_cap
+        pn = self.text_bytes(1) if pests_cap is None else pests_cap
+        out = np.zeros(max(n_units, 1), dtype=np.dtype(TEXT_RESULT_DTYPE))
+        raw, pests = np.zeros(max(rn, 1), dtype=np.uint8), np.zeros(max(pn, 1), dtype=np.uint8)
+        rc = self.ctx.L.pgpu_pairing_plan_fetch_texts(self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(TextResult)),
+                                                      raw.ctypes.data_as(C.c_void_p), rn, pests.ctypes.data_as(C.c_void_p), pn)
+        return rc, out[:n_units], raw[:rn], pests[:pn]
+
+    def fetch_texts(self):
+        rc, out, raw, pests = self.fetch_texts_raw(self._n_units)
+        self.ctx.check(rc)
+        return out, raw.tobytes(), pests.tobytes()
+
+    def texts_ms(self):
+        """HIP-event time of the last run_texts (count + scans + write)"""
+        return self.ctx.L.pgpu_pairing_plan_texts_ms(self.h)
+
+    def texts_write_ms(self):
+        """HIP-event time of the write pass of the last run_texts"""
+        return self.ctx.L.pgpu_pairing_plan_texts_write_ms(self.h)
 
     def close(self):
         if self.h:

@@ -93,6 +93,7 @@ enum PlanSlot : int {
   SLOT_FACT, SLOT_FACT_WS,
   SLOT_ORIG_OFF, SLOT_FINAL,
   SLOT_UNITS,
+  SLOT_TEXTS, SLOT_TEXT_BLOBS,
   PLAN_SLOTS
 };
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool);
@@ -197,6 +198,27 @@ struct pgpu_unit_job {
   unsigned long long total;
 };
 hipError_t pgpu_unit_drive(pgpu_ctx* ctx, pgpu_unit_job& job);
+// pgpu_text.hip: the units and their groups (`units`, `blob`: read only, where they lie) to the two texts of every ALIGNED
+// unit.  Sequence p is seqs[seq_at[p] ..) of seq_off[p + 1] - seq_off[p] bytes (the form without a plan: both are its
+// seq_first; a plan: its table of original offsets and its pattern offsets).  Behind headers, sequences and genomic lie
+// 16 readable bytes.  `block` holds text_layout(n, headers_len, pgpu_scan_tmp_bytes(n + 1)).total bytes (pgpu_text.h) with
+// the headers and their offsets already in place.  pgpu_text_count runs the count pass and the two scans and ends with the
+// stage's one host wait: the totals are set on return.  pgpu_text_write queues the write pass into two blobs of at
+// least those sizes, and waits for nothing.
+struct pgpu_text_job {
+  const pgpu_unit_result* units; uint32_t n;
+  const uint8_t* blob; unsigned long long blob_len;
+  size_t headers_len;
+  const uint8_t* seqs; const unsigned long long* seq_at; const unsigned long long* seq_off; uint32_t n_pat;
+  const uint8_t* genomic; unsigned long long genomic_len;
+  uint8_t* block;
+  hipEvent_t ev[3];            // null without timing: 0-1 around count + scans + write, 2 in front of the write pass
+  unsigned long long raw_total, pests_total;
+};
+hipError_t pgpu_text_count(pgpu_ctx* ctx, pgpu_text_job& job);
+hipError_t pgpu_text_write(pgpu_ctx* ctx, const pgpu_text_job& job, uint8_t* raw, uint8_t* pests);
+// the genomic sequence of pgpu_text_source_create: device pointer (16 readable bytes behind it), length, owner
+struct pgpu_text_source { pgpu_ctx* owner; uint8_t* d; size_t len; };
 // PGPU_TRACE_ALLOC=1: every page-locked host allocation of the library on stderr (size, address, call site)
 static inline void pgpu_trace_alloc(const char* what, const void* q, size_t bytes) {
   static int on = -1;

@@ -23,6 +23,7 @@
 #include "pgpu_fact.h"
 #include "pgpu_final.h"
 #include "pgpu_unit.h"
+#include "pgpu_text.h"
 #include "pgpu_small.h"
 #include "pgpu_classify.h"
 
@@ -369,11 +370,12 @@ void pair_emit_kernel(const unsigned long long* __restrict__ pat_off,
 // compare one), and raises the plan to k when it succeeds.  A fetch of stage k asks for stage k.  A plan without
 // patterns has nothing to compute: its runs succeed without their predecessor (run_factorizations and the stages above
 // it still ask for theirs), and fetch and fetch_meg answer whatever ran.
-enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS, UNITS };
+enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS, UNITS, TEXTS };
 
 // the plan's events (made only when the context times its calls): seven around the six pairing stages, a pair each for
-// the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job, the pair of pgpu_unit_job
-enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, N_EVENTS = 27 };
+// the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job, the pair of pgpu_unit_job, the
+// three of pgpu_text_job
+enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, EV_TEXTS = 27, N_EVENTS = 30 };
 
 struct pgpu_pairing_plan {
   pgpu_ctx* owner = nullptr;
@@ -439,6 +441,13 @@ struct pgpu_pairing_plan {
   size_t unit_cap = 0, n_units = 0;
   unsigned long long unit_total = 0;
   float unit_ms = 0.f;
+  // text stage (pgpu_text.hip) over the units of the last run_units: the stage's block, and the two blobs (raw, then pests
+  // at text_pests_at), which are sized after the count pass
+  uint8_t *d_text = nullptr, *d_text_blobs = nullptr;
+  size_t text_cap = 0, text_blobs_cap = 0, text_pests_at = 0, text_headers_len = 0;
+  unsigned long long text_raw_total = 0, text_pests_total = 0;
+  bool text_timed = false;                             // the write pass's event is still to be waited for
+  float text_ms = 0.f, text_write_ms = 0.f;
 };
 
 static void lower(pgpu_pairing_plan* p, Stage s) { if (p->stage > s) p->stage = s; }
@@ -524,7 +533,7 @@ static hipError_t scan_total(pgpu_ctx* ctx, const pgpu_pairing_plan* p, uint32_t
   return pgpu_ctx_wait(ctx);
 }
 
-// the one block of a rung from four to six, with an eighth to spare; a resident plan takes it anew: the pool may have moved
+// the one block of a rung from four to seven, with an eighth to spare; a resident plan takes it anew: the pool may have moved
 static uint8_t* stage_block(pgpu_pairing_plan* p, uint8_t* ptr, size_t* cap, size_t total, PlanSlot slot) {
   return plan_grow(p, p->resident ? nullptr : ptr, cap, total, total / 8, slot);
 }
@@ -544,7 +553,7 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_keep); hipFree(p->d_out); hipFree(p->d_tmp);
     hipFree(p->d_meg_scratch); hipFree(p->d_meg_info); hipFree(p->d_meg_bytes); hipFree(p->d_meg_off); hipFree(p->d_meg_out);
     hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
-    hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final); hipFree(p->d_unit);
+    hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final); hipFree(p->d_unit); hipFree(p->d_text); hipFree(p->d_text_blobs);
     if (p->d_orig_off != p->d_pat_off) hipFree(p->d_orig_off);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
@@ -964,6 +973,87 @@ extern "C" int pgpu_pairing_plan_fetch_units(pgpu_ctx* ctx, pgpu_pairing_plan* p
   PLAN_TRY(hipMemcpyAsync(out, p->d_unit + L.out, p->n_units * sizeof(pgpu_unit_result), hipMemcpyDeviceToHost, st));
   if (p->unit_total) PLAN_TRY(hipMemcpyAsync(blob, p->d_unit + L.blob, (size_t)p->unit_total, hipMemcpyDeviceToHost, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
+  return PGPU_OK;
+}
+
+// ---- the units of the last run_units to est-fact's two text files, where they lie (pgpu_text.hip) -----------------------
+extern "C" int pgpu_pairing_plan_run_texts(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_text_source* src, const char* headers,
+                                           size_t headers_len, const uint64_t* hdr_first) {
+  if (!ctx || !p || !src || (p->n_units && !hdr_first) || (headers_len && !headers)) return PGPU_EINVAL;
+  p->text_raw_total = p->text_pests_total = 0; p->text_ms = p->text_write_ms = 0.f; p->text_timed = false;
+  lower(p, UNITS);
+  if (src->owner != ctx) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "this text source was made on another context");
+  if (p->stage < UNITS) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_texts needs the units of pgpu_pairing_plan_run_units");
+  const size_t n_units = p->n_units;
+  if (hdr_first)
+    if (const char* wrong = text_offsets_wrong(hdr_first, n_units, headers_len, TEXT_BAD_HDR)) return pgpu_ctx_fail(ctx, PGPU_EINVAL, wrong);
+  if (p->n_pat == 0 || n_units == 0) return reached(p, TEXTS);
+  if (const int rc = still_owns(ctx, p, "units")) return rc;
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  const ProfRange range("texts");
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  const TextLayout L = text_layout(n_units, headers_len, pgpu_scan_tmp_bytes(n_units + 1));
+  PLAN_NEED(p->d_text = stage_block(p, p->d_text, &p->text_cap, L.total, SLOT_TEXTS));
+  PLAN_TRY(plan_events(p, EV_TEXTS, 3));
+  // the headers are uploaded at every run: about 30 bytes per unit
+  if (headers_len) PLAN_TRY(hipMemcpyAsync(p->d_text + L.hdr, headers, headers_len, hipMemcpyHostToDevice, st));
+  PLAN_TRY(hipMemcpyAsync(p->d_text + L.hdr_first, hdr_first, (n_units + 1) * sizeof *hdr_first, hipMemcpyHostToDevice, st));
+  const UnitLayout U = unit_layout(n_units, (size_t)p->final_total, pgpu_scan_tmp_bytes(n_units + 1));
+  pgpu_text_job job;
+  job.units = (const pgpu_unit_result*)(p->d_unit + U.out); job.n = (uint32_t)n_units;
+  job.blob = p->d_unit + U.blob; job.blob_len = p->unit_total; job.headers_len = headers_len;
+  job.seqs = p->d_pats; job.seq_at = p->d_orig_off; job.seq_off = p->d_pat_off; job.n_pat = (uint32_t)p->n_pat;
+  job.genomic = src->d; job.genomic_len = src->len;
+  job.block = p->d_text;
+  for (int k = 0; k < 3; ++k) job.ev[k] = p->ev[EV_TEXTS + k];
+  PLAN_TRY(pgpu_text_count(ctx, job));                 // the call's one host wait
+  const size_t raw = (size_t)job.raw_total, pests = (size_t)job.pests_total, o_pests = up256(raw ? raw : 1);
+  PLAN_NEED(p->d_text_blobs = stage_block(p, p->d_text_blobs, &p->text_blobs_cap, o_pests + up256(pests ? pests : 1), SLOT_TEXT_BLOBS));
+  PLAN_TRY(pgpu_text_write(ctx, job, p->d_text_blobs, p->d_text_blobs + o_pests));
+  p->text_raw_total = job.raw_total; p->text_pests_total = job.pests_total; p->text_pests_at = o_pests;
+  p->text_headers_len = headers_len; p->text_timed = p->ev[EV_TEXTS] != nullptr;
+  return reached(p, TEXTS);
+}
+
+extern "C" uint64_t pgpu_pairing_plan_text_bytes(const pgpu_pairing_plan* p, int which) {
+  return !p ? 0 : which == 0 ? p->text_raw_total : which == 1 ? p->text_pests_total : 0;
+}
+// the run did not wait for its write pass: the first question about its time does
+static void text_times(pgpu_pairing_plan* p) {
+  if (!p->text_timed || p->stage < TEXTS) return;
+  p->text_timed = false;
+  if (hipEventSynchronize(p->ev[EV_TEXTS + 1]) != hipSuccess) return;
+  elapsed_pairs(p, EV_TEXTS, 1, &p->text_ms);
+  hipEventElapsedTime(&p->text_write_ms, p->ev[EV_TEXTS + 2], p->ev[EV_TEXTS + 1]);
+}
+extern "C" double pgpu_pairing_plan_texts_ms(pgpu_pairing_plan* p) {
+  if (!p) return 0.0;
+  text_times(p);
+  return p->text_ms;
+}
+extern "C" double pgpu_pairing_plan_texts_write_ms(pgpu_pairing_plan* p) {
+  if (!p) return 0.0;
+  text_times(p);
+  return p->text_write_ms;
+}
+
+extern "C" int pgpu_pairing_plan_fetch_texts(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_text_result* out, void* raw, size_t raw_cap,
+                                             void* pests, size_t pests_cap) {
+  if (!ctx || !p || (raw_cap && !raw) || (pests_cap && !pests)) return PGPU_EINVAL;
+  if (p->stage < TEXTS) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_texts needs pgpu_pairing_plan_run_texts first");
+  if (p->n_pat && p->n_units && !out) return PGPU_EINVAL;
+  if (const int rc = still_owns(ctx, p, "results")) return rc;
+  if (raw_cap < p->text_raw_total || pests_cap < p->text_pests_total) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "text buffers too small");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_pat == 0 || p->n_units == 0) return PGPU_OK;
+  const TextLayout L = text_layout(p->n_units, p->text_headers_len, pgpu_scan_tmp_bytes(p->n_units + 1));
+  PLAN_TRY(hipMemcpyAsync(out, p->d_text + L.out, p->n_units * sizeof(pgpu_text_result), hipMemcpyDeviceToHost, st));
+  if (p->text_raw_total) PLAN_TRY(hipMemcpyAsync(raw, p->d_text_blobs, (size_t)p->text_raw_total, hipMemcpyDeviceToHost, st));
+  if (p->text_pests_total)
+    PLAN_TRY(hipMemcpyAsync(pests, p->d_text_blobs + p->text_pests_at, (size_t)p->text_pests_total, hipMemcpyDeviceToHost, st));
+  PLAN_TRY(pgpu_ctx_wait(ctx));
+  PLAN_TRY(hipGetLastError());
   return PGPU_OK;
 }
 
