@@ -1173,6 +1173,91 @@ double pgpu_pairing_plan_texts_ms(pgpu_pairing_plan* plan);
 /* the write pass alone, the same way */
 double pgpu_pairing_plan_texts_write_ms(pgpu_pairing_plan* plan);
 
+/* ------------------------------------------------------------------------------------------ */
+/* sides -- from a unit's MEG records to est-fact's three side files: the entries of megs.txt   */
+/* and processed-megs.txt and the lines of meg-edges.txt (report_meg and the writes behind it,  */
+/* src/compute-est-fact.c:73-88, 240-268; pintron_amd/host/ef_estfact.c: ef_compute_est_fact).  */
+/* A MEG record ends with meg_write's text and the meg-edges.txt lines of its graph, so the     */
+/* stage is the rule for which entries an input EST gets, and copying.  processed-megs-info.txt */
+/* holds per-EST microseconds and is not part of this stage.  Nothing in the library calls      */
+/* these entries yet.                                                                           */
+/* ------------------------------------------------------------------------------------------ */
+#define PGPU_SIDE_MAX_UNIT_BYTES (1u << 24)
+#define PGPU_SIDE_NONE 0u   /* the unit is HOST: no bytes in any blob */
+#define PGPU_SIDE_DONE 1u   /* the three texts are written */
+#define PGPU_SIDE_HOST 2u   /* one of the three texts is longer than PGPU_SIDE_MAX_UNIT_BYTES, or (below) the unit is not one
+                               the rule covers: no bytes, the caller prints this EST */
+typedef struct {
+  uint64_t megs_first, pmegs_first, edges_first;   /* DONE only, else 0: where the unit's texts begin in the three blobs */
+  uint32_t megs_bytes, pmegs_bytes, edges_bytes;   /* DONE only, else 0 */
+  uint8_t  verdict;                                /* PGPU_SIDE_* */
+  uint8_t  reserved[3];
+} pgpu_side_result;         /* 40 bytes */
+
+/* The rule.  For a unit u with forward pattern f = q.fwd and sibling r = q.rev: H is the unit's header bytes (ef_seq.id,
+ * the same for both strands: ef_copy_and_reverse), S_x the original sequence of pattern x, M_x the meg_text_len bytes of
+ * pattern x's MEG record (the record of the FIRST attempt: a settled unit was never retried), X_x the edges_text_len bytes
+ * behind them, SEP = "\n\n***********\n\n" (15 bytes), and E(x) = ">" H "\n" S_x "\n" M_x.
+ *    unit verdict, strand         megs(u)                pmegs(u)   edges(u)
+ *    ALIGNED, 0                   SEP E(f)               E(f)       ">" H "\n" X_f
+ *    ALIGNED, 1                   SEP E(f) SEP E(r)      E(r)       ">" H "\n" X_r
+ *    UNALIGNED, 0 (no sibling)    SEP E(f)               empty      empty
+ *    UNALIGNED, 1                 SEP E(f) SEP E(r)      empty      empty
+ *    HOST                         no bytes               no bytes   no bytes
+ *  - An UNALIGNED unit does have an entry of megs.txt (in this the stage differs from the text stage).  A HOST unit has no
+ *    bytes because the host's own path may build that EST's MEG again with a longer factor.
+ *  - Per unit one pgpu_side_result: NONE for a HOST unit; HOST when megs(u), pmegs(u) or edges(u) is longer than
+ *    PGPU_SIDE_MAX_UNIT_BYTES (the count formed in 64 bits), and for an UNALIGNED unit of strand 0 that has a sibling
+ *    (est-fact never leaves such an EST: it goes on to the sibling); DONE otherwise.  The three blobs are compact and in
+ *    UNIT order, whatever the pattern order: a call whose units are all settled produces est-fact's three files for those
+ *    ESTs byte for byte. */
+
+/* The form without a plan: fetched or host-made records.  q / units: the n queries and results of the unit stage; recs:
+ * recs_len bytes and rec_first: n_pat + 1 offsets, as pgpu_pairing_plan_fetch_meg gives them; headers: headers_len bytes,
+ * hdr_first: n + 1 offsets, unit i's header is headers[hdr_first[i] .. hdr_first[i+1]); seqs: seqs_len bytes, seq_first:
+ * n_pat + 1 offsets, one (original) sequence per pattern; out: n results; megs / pmegs / edges: their caps in bytes;
+ * lens[0 .. 3): bytes written to the three.  One upload, one download; synchronous.
+ *  - PGPU_EINVAL for the whole call, for structure only: a null pointer (no message); offsets that do not ascend or that
+ *    pass their length; a rec_first that is no multiple of 4; a verdict above 2 or a strand above 1; fwd or rev >= n_pat
+ *    (rev may be PGPU_UNIT_NO_SIBLING); strand 1 on a unit without a sibling; units[i].pattern other than the query's
+ *    pattern of that strand; a settled unit (not HOST) naming a record -- f, and r too on strand 1 -- that is flagged
+ *    (PGPU_MEG_TOO_COMPLEX, PGPU_MEG_UNAVAILABLE), or whose graph part, 8 bytes of lengths and two texts pass
+ *    rec_first[x + 1]; more than 2^31 - 1 units or patterns.
+ *  - PGPU_ENOSPC, with the three needed sizes in lens and nothing written to out, megs, pmegs or edges, when a cap is
+ *    too small.
+ *  - n == 0 is PGPU_OK (all three lengths 0). */
+int pgpu_unit_sides(pgpu_ctx* ctx, const pgpu_unit_query* q, const pgpu_unit_result* units, size_t n,
+                    const void* recs, size_t recs_len, const uint64_t* rec_first, size_t n_pat,
+                    const char* headers, size_t headers_len, const uint64_t* hdr_first,
+                    const char* seqs, size_t seqs_len, const uint64_t* seq_first,
+                    pgpu_side_result* out, void* megs, size_t megs_cap, void* pmegs, size_t pmegs_cap,
+                    void* edges, size_t edges_cap, size_t lens[3]);
+/* HIP-event time of the kernels of the calling thread's last pgpu_unit_sides on a context with timing on (as
+ * pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_unit_sides_kernel_ms(void);
+
+/* Plan form, the eighth stage of a plan: no arguments, because everything lies in HBM already -- the records and their
+ * offsets of the last run_meg, the queries and results of the last run_units, the headers and their offsets where the last
+ * run_texts left them (so they do not travel a second time: this is why the stage stands above the texts and not beside
+ * them), and the plan's originals (a pattern's own bytes where it has none).  A PGPU_TEXT_HOST verdict of the text stage
+ * does not matter to this one.  Here a settled unit that names a record which is flagged or does not add up is
+ * PGPU_SIDE_HOST (the form without a plan refuses it).  Texts, units and finals stay fetchable and unchanged; a run of any
+ * earlier stage, run_texts included, takes the sides with it.  PGPU_EINVAL (with a message): no run_texts since the last
+ * run of an earlier stage; the results of a resident plan were overwritten by the run of another one; fetch before the
+ * run.  A null pointer is a bare PGPU_EINVAL.  An empty plan or a run of zero units is PGPU_OK.  A rerun gives the same
+ * bytes.  The one host wait of the call is for the three byte totals that size the blobs: the write pass is still queued
+ * when the call returns, and fetch_sides (or sides_ms) waits for it. */
+int pgpu_pairing_plan_run_sides(pgpu_ctx* ctx, pgpu_pairing_plan* plan);
+/* bytes of a blob of the last run_sides: which == 0 megs, 1 pmegs, 2 edges, anything else 0 */
+uint64_t pgpu_pairing_plan_side_bytes(const pgpu_pairing_plan* plan, int which);
+/* out: as many results as the last run_units had units; PGPU_ENOSPC when a cap is smaller than its side_bytes */
+int pgpu_pairing_plan_fetch_sides(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_side_result* out, void* megs, size_t megs_cap,
+                                  void* pmegs, size_t pmegs_cap, void* edges, size_t edges_cap);
+/* HIP-event time of the last run_sides (count + scans + write; waits for the write pass); 0 without timing */
+double pgpu_pairing_plan_sides_ms(pgpu_pairing_plan* plan);
+/* the write pass alone, the same way */
+double pgpu_pairing_plan_sides_write_ms(pgpu_pairing_plan* plan);
+
 /* page-locked host memory for the buffers handed to the fetch calls (a pageable destination
  * makes the runtime stage the copy); plain malloc'ed memory works too, slower */
 int pgpu_host_alloc(pgpu_ctx* ctx, size_t bytes, void** out);

@@ -176,6 +176,11 @@ class TextResult(C.Structure):     # pgpu_text_result
                 ("verdict", C.c_uint8), ("reserved", C.c_uint8 * 7)]
 
 
+class SideResult(C.Structure):     # pgpu_side_result
+    _fields_ = [("megs_first", C.c_uint64), ("pmegs_first", C.c_uint64), ("edges_first", C.c_uint64), ("megs_bytes", C.c_uint32),
+                ("pmegs_bytes", C.c_uint32), ("edges_bytes", C.c_uint32), ("verdict", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 REFINE_MAX_DIM, REFINE_MAX_ED, REFINE_FIRST_INTRON = 1024, 256, 1
 CHAIN_MAX_EST_WINDOW, CHAIN_MAX_GEN_WINDOW = 192, 320
 _FACTOR_DTYPE = [("EST_start", "<i4"), ("EST_end", "<i4"), ("GEN_start", "<i4"), ("GEN_end", "<i4")]
@@ -230,6 +235,10 @@ TEXT_NONE, TEXT_DONE, TEXT_HOST = range(3)
 TEXT_MAX_UNIT_BYTES = 1 << 24
 TEXT_RESULT_DTYPE = [("raw_first", "<u8"), ("pests_first", "<u8"), ("raw_bytes", "<u4"), ("pests_bytes", "<u4"), ("verdict", "u1"),
                      ("reserved", "u1", (7,))]
+SIDE_NONE, SIDE_DONE, SIDE_HOST = range(3)
+SIDE_MAX_UNIT_BYTES = 1 << 24
+SIDE_RESULT_DTYPE = [("megs_first", "<u8"), ("pmegs_first", "<u8"), ("edges_first", "<u8"), ("megs_bytes", "<u4"), ("pmegs_bytes", "<u4"),
+                     ("edges_bytes", "<u4"), ("verdict", "u1"), ("reserved", "u1", (3,))]
 UNIT_QUERY_DTYPE = [("est_index", "<u4"), ("fwd", "<u4"), ("rev", "<u4"), ("flags", "<u4")]
 UNIT_RESULT_DTYPE = [("verdict", "u1"), ("strand", "u1"), ("reason", "u1"), ("n_factorizations", "u1"), ("pattern", "<u4"),
                      ("first_byte", "<u8"), ("n_bytes", "<u4"), ("reserved", "<u4")]
@@ -253,6 +262,7 @@ assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
 assert C.sizeof(FinalResult) == 32 and C.sizeof(FinalQuery) == 32
 assert C.sizeof(UnitQuery) == 16 and C.sizeof(UnitParams) == 8 and C.sizeof(UnitResult) == 24
 assert C.sizeof(TextResult) == 32
+assert C.sizeof(SideResult) == 40
 
 # every symbol include/pintron_gpu.h declares
 EXPORTS = [
@@ -283,6 +293,8 @@ EXPORTS = [
     "pgpu_text_source_create", "pgpu_text_source_destroy", "pgpu_unit_texts", "pgpu_unit_texts_kernel_ms",
     "pgpu_pairing_plan_run_texts", "pgpu_pairing_plan_text_bytes", "pgpu_pairing_plan_fetch_texts", "pgpu_pairing_plan_texts_ms",
     "pgpu_pairing_plan_texts_write_ms",
+    "pgpu_unit_sides", "pgpu_unit_sides_kernel_ms", "pgpu_pairing_plan_run_sides", "pgpu_pairing_plan_side_bytes",
+    "pgpu_pairing_plan_fetch_sides", "pgpu_pairing_plan_sides_ms", "pgpu_pairing_plan_sides_write_ms",
     "pgpu_comm_unique_id", "pgpu_comm_init", "pgpu_gather", "pgpu_allgather", "pgpu_comm_destroy",
     "pgpu_range_push", "pgpu_range_pop", "pgpu_build_info",
     "pgpu_dp_plan_create", "pgpu_dp_plan_create_parts", "pgpu_dp_plan_launch", "pgpu_dp_plan_sync",
@@ -426,6 +438,19 @@ def lib():
         L.pgpu_pairing_plan_texts_ms.restype = C.c_double
         L.pgpu_pairing_plan_texts_write_ms.argtypes = [vp]
         L.pgpu_pairing_plan_texts_write_ms.restype = C.c_double
+        L.pgpu_unit_sides.argtypes = [vp, C.POINTER(UnitQuery), C.POINTER(UnitResult), sz, vp, sz, C.POINTER(u64), sz, vp, sz,
+                                      C.POINTER(u64), vp, sz, C.POINTER(u64), C.POINTER(SideResult), vp, sz, vp, sz, vp, sz,
+                                      C.POINTER(sz)]
+        L.pgpu_unit_sides_kernel_ms.argtypes = []
+        L.pgpu_unit_sides_kernel_ms.restype = C.c_double
+        L.pgpu_pairing_plan_run_sides.argtypes = [vp, vp]
+        L.pgpu_pairing_plan_side_bytes.argtypes = [vp, C.c_int]
+        L.pgpu_pairing_plan_side_bytes.restype = u64
+        L.pgpu_pairing_plan_fetch_sides.argtypes = [vp, vp, C.POINTER(SideResult), vp, sz, vp, sz, vp, sz]
+        L.pgpu_pairing_plan_sides_ms.argtypes = [vp]
+        L.pgpu_pairing_plan_sides_ms.restype = C.c_double
+        L.pgpu_pairing_plan_sides_write_ms.argtypes = [vp]
+        L.pgpu_pairing_plan_sides_write_ms.restype = C.c_double
         L.pgpu_host_alloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.pgpu_host_free.argtypes = [vp, vp]
         L.pgpu_comm_unique_id.argtypes = [vp, vp]
@@ -927,6 +952,43 @@ def unit_texts(ctx, units, blob, headers, seqs, genomic):
     return out, raw[:raw_len].tobytes(), pests[:pests_len].tobytes()
 
 
+def unit_sides_raw(ctx, q, units, n, recs, rec_first, n_pat, headers, hdr_first, seqs, seq_first, caps,
+                   recs_len=None, headers_len=None, seqs_len=None):
+    """One pgpu_unit_sides call as it is: `q` a numpy array of UNIT_QUERY_DTYPE, `units` one of UNIT_RESULT_DTYPE, `recs`,
+    `headers`, `seqs` bytes, `rec_first`, `hdr_first` and `seq_first` numpy uint64 arrays, `caps` the three caps.  Returns
+    (rc, results as a numpy array of SIDE_RESULT_DTYPE, the three blobs as numpy uint8 arrays of their caps, the three
+    lengths)."""
+    import numpy as np
+    out = np.zeros(min(n, len(units)), dtype=np.dtype(SIDE_RESULT_DTYPE))
+    blobs = [np.zeros(c, dtype=np.uint8) for c in caps]
+    lens = (C.c_size_t * 3)(0, 0, 0)
+    b = lambda x: C.cast(C.c_char_p(x), C.c_void_p)
+    rc = ctx.L.pgpu_unit_sides(
+        ctx.h, q.ctypes.data_as(C.POINTER(UnitQuery)), units.ctypes.data_as(C.POINTER(UnitResult)), n,
+        b(recs), len(recs) if recs_len is None else recs_len, rec_first.ctypes.data_as(C.POINTER(C.c_uint64)), n_pat,
+        b(headers), len(headers) if headers_len is None else headers_len, hdr_first.ctypes.data_as(C.POINTER(C.c_uint64)),
+        b(seqs), len(seqs) if seqs_len is None else seqs_len, seq_first.ctypes.data_as(C.POINTER(C.c_uint64)),
+        out.ctypes.data_as(C.POINTER(SideResult)), blobs[0].ctypes.data_as(C.c_void_p), caps[0],
+        blobs[1].ctypes.data_as(C.c_void_p), caps[1], blobs[2].ctypes.data_as(C.c_void_p), caps[2], lens)
+    return rc, out, blobs, tuple(lens)
+
+
+def unit_sides(ctx, q, units, records, headers, seqs):
+    """The three side texts of every settled unit: `q` and `units` numpy arrays of UNIT_QUERY_DTYPE and UNIT_RESULT_DTYPE,
+    `records` one bytes per pattern (as PairingPlan.fetch_meg gives them), `headers` one bytes per unit, `seqs` one
+    (original) sequence per pattern -> (results as a numpy array of SIDE_RESULT_DTYPE, megs, pmegs, edges as bytes).  Two
+    calls: the first one asks for the sizes."""
+    rb, rf = _offsets(records)
+    hb, hf = _offsets(headers)
+    sb, sf = _offsets(seqs)
+    args = (ctx, q, units, len(units), rb, rf, len(records), hb, hf, sb, sf)
+    rc, out, blobs, lens = unit_sides_raw(*args, (0, 0, 0))
+    if rc == PGPU_ENOSPC:
+        rc, out, blobs, lens = unit_sides_raw(*args, lens)
+    ctx.check(rc)
+    return (out,) + tuple(b[:n].tobytes() for b, n in zip(blobs, lens))
+
+
 class TextSource:
     """The original genomic sequence in HBM, for PairingPlan.run_texts"""
 
@@ -1189,6 +1251,42 @@ class PairingPlan:
     def texts_write_ms(self):
         """HIP-event time of the write pass of the last run_texts"""
         return self.ctx.L.pgpu_pairing_plan_texts_write_ms(self.h)
+
+    def run_sides_raw(self):
+        return self.ctx.L.pgpu_pairing_plan_run_sides(self.ctx.h, self.h)
+
+    def run_sides(self):
+        """the records of the units of the last run_units, with the headers of the last run_texts, to est-fact's three side
+        texts, where they lie -> (bytes of megs, of pmegs, of edges)"""
+        self.ctx.check(self.run_sides_raw())
+        return tuple(self.side_bytes(k) for k in range(3))
+
+    def side_bytes(self, which):
+        return self.ctx.L.pgpu_pairing_plan_side_bytes(self.h, which)
+
+    def fetch_sides_raw(self, n_units, caps=None):
+        """(rc, results as a numpy array of SIDE_RESULT_DTYPE, one per unit; megs, pmegs and edges as numpy uint8 arrays)"""
+        import numpy as np
+        caps = [self.side_bytes(k) for k in range(3)] if caps is None else list(caps)
+        out = np.zeros(max(n_units, 1), dtype=np.dtype(SIDE_RESULT_DTYPE))
+        blobs = [np.zeros(max(c, 1), dtype=np.uint8) for c in caps]
+        rc = self.ctx.L.pgpu_pairing_plan_fetch_sides(
+            self.ctx.h, self.h, out.ctypes.data_as(C.POINTER(SideResult)), blobs[0].ctypes.data_as(C.c_void_p), caps[0],
+            blobs[1].ctypes.data_as(C.c_void_p), caps[1], blobs[2].ctypes.data_as(C.c_void_p), caps[2])
+        return rc, out[:n_units], [b[:c] for b, c in zip(blobs, caps)]
+
+    def fetch_sides(self):
+        rc, out, blobs = self.fetch_sides_raw(self._n_units)
+        self.ctx.check(rc)
+        return (out,) + tuple(b.tobytes() for b in blobs)
+
+    def sides_ms(self):
+        """HIP-event time of the last run_sides (count + scans + write)"""
+        return self.ctx.L.pgpu_pairing_plan_sides_ms(self.h)
+
+    def sides_write_ms(self):
+        """HIP-event time of the write pass of the last run_sides"""
+        return self.ctx.L.pgpu_pairing_plan_sides_write_ms(self.h)
 
     def close(self):
         if self.h:

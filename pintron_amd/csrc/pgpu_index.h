@@ -94,6 +94,7 @@ enum PlanSlot : int {
   SLOT_ORIG_OFF, SLOT_FINAL,
   SLOT_UNITS,
   SLOT_TEXTS, SLOT_TEXT_BLOBS,
+  SLOT_SIDES, SLOT_SIDE_BLOBS,
   PLAN_SLOTS
 };
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool);
@@ -219,6 +220,24 @@ hipError_t pgpu_text_count(pgpu_ctx* ctx, pgpu_text_job& job);
 hipError_t pgpu_text_write(pgpu_ctx* ctx, const pgpu_text_job& job, uint8_t* raw, uint8_t* pests);
 // the genomic sequence of pgpu_text_source_create: device pointer (16 readable bytes behind it), length, owner
 struct pgpu_text_source { pgpu_ctx* owner; uint8_t* d; size_t len; };
+// pgpu_side.hip: the queries and results of the unit stage (`q`, `units`: read only, where they lie) and the MEG records of
+// the patterns (`recs`: recs_len bytes, record p at rec_first[p], n_pat + 1 offsets, every one a multiple of 4 and the base
+// a multiple of 256) to the three side texts of every settled unit.  Headers (`hdr`, n + 1 offsets `hdr_first`) and
+// sequences (as in pgpu_text_job) are read where they lie, with 16 readable bytes behind them.  `block` holds
+// side_layout(n, pgpu_scan_tmp_bytes(n + 1)).total bytes (pgpu_side.h).  pgpu_side_count runs the count pass and the three
+// scans and ends with the stage's one host wait: total[0 .. 3) are set on return.  pgpu_side_write queues the write pass
+// into three blobs of at least those sizes, and waits for nothing.
+struct pgpu_side_job {
+  const pgpu_unit_query* q; const pgpu_unit_result* units; uint32_t n;
+  const uint8_t* recs; unsigned long long recs_len; const unsigned long long* rec_first; uint32_t n_pat;
+  const uint8_t* hdr; const unsigned long long* hdr_first;
+  const uint8_t* seqs; const unsigned long long* seq_at; const unsigned long long* seq_off;
+  uint8_t* block;
+  hipEvent_t ev[3];            // null without timing: 0-1 around count + scans + write, 2 in front of the write pass
+  unsigned long long total[3]; // megs, pmegs, edges
+};
+hipError_t pgpu_side_count(pgpu_ctx* ctx, pgpu_side_job& job);
+hipError_t pgpu_side_write(pgpu_ctx* ctx, const pgpu_side_job& job, uint8_t* megs, uint8_t* pmegs, uint8_t* edges);
 // PGPU_TRACE_ALLOC=1: every page-locked host allocation of the library on stderr (size, address, call site)
 static inline void pgpu_trace_alloc(const char* what, const void* q, size_t bytes) {
   static int on = -1;

@@ -23,6 +23,7 @@
 #include "pgpu_fact.h"
 #include "pgpu_final.h"
 #include "pgpu_unit.h"
+#include "pgpu_side.h"
 #include "pgpu_text.h"
 #include "pgpu_small.h"
 #include "pgpu_classify.h"
@@ -370,12 +371,12 @@ void pair_emit_kernel(const unsigned long long* __restrict__ pat_off,
 // compare one), and raises the plan to k when it succeeds.  A fetch of stage k asks for stage k.  A plan without
 // patterns has nothing to compute: its runs succeed without their predecessor (run_factorizations and the stages above
 // it still ask for theirs), and fetch and fetch_meg answer whatever ran.
-enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS, UNITS, TEXTS };
+enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS, UNITS, TEXTS, SIDES };
 
 // the plan's events (made only when the context times its calls): seven around the six pairing stages, a pair each for
 // the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job, the pair of pgpu_unit_job, the
-// three of pgpu_text_job
-enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, EV_TEXTS = 27, N_EVENTS = 30 };
+// three of pgpu_text_job, the three of pgpu_side_job
+enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, EV_TEXTS = 27, EV_SIDES = 30, N_EVENTS = 33 };
 
 struct pgpu_pairing_plan {
   pgpu_ctx* owner = nullptr;
@@ -448,6 +449,13 @@ struct pgpu_pairing_plan {
   unsigned long long text_raw_total = 0, text_pests_total = 0;
   bool text_timed = false;                             // the write pass's event is still to be waited for
   float text_ms = 0.f, text_write_ms = 0.f;
+  // side stage (pgpu_side.hip) over the records of the last run_meg, the units of the last run_units and the headers of the
+  // last run_texts: the stage's block, and the three blobs in one allocation (side_blobs), sized after the count pass
+  uint8_t *d_side = nullptr, *d_side_blobs = nullptr;
+  size_t side_cap = 0, side_blobs_cap = 0;
+  unsigned long long side_total[3] = {0, 0, 0};
+  bool side_timed = false;                             // the write pass's event is still to be waited for
+  float side_ms = 0.f, side_write_ms = 0.f;
 };
 
 static void lower(pgpu_pairing_plan* p, Stage s) { if (p->stage > s) p->stage = s; }
@@ -533,7 +541,7 @@ static hipError_t scan_total(pgpu_ctx* ctx, const pgpu_pairing_plan* p, uint32_t
   return pgpu_ctx_wait(ctx);
 }
 
-// the one block of a rung from four to seven, with an eighth to spare; a resident plan takes it anew: the pool may have moved
+// the one block of a rung from four to eight, with an eighth to spare; a resident plan takes it anew: the pool may have moved
 static uint8_t* stage_block(pgpu_pairing_plan* p, uint8_t* ptr, size_t* cap, size_t total, PlanSlot slot) {
   return plan_grow(p, p->resident ? nullptr : ptr, cap, total, total / 8, slot);
 }
@@ -554,6 +562,7 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_meg_scratch); hipFree(p->d_meg_info); hipFree(p->d_meg_bytes); hipFree(p->d_meg_off); hipFree(p->d_meg_out);
     hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
     hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final); hipFree(p->d_unit); hipFree(p->d_text); hipFree(p->d_text_blobs);
+    hipFree(p->d_side); hipFree(p->d_side_blobs);
     if (p->d_orig_off != p->d_pat_off) hipFree(p->d_orig_off);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
@@ -1052,6 +1061,82 @@ extern "C" int pgpu_pairing_plan_fetch_texts(pgpu_ctx* ctx, pgpu_pairing_plan* p
   if (p->text_raw_total) PLAN_TRY(hipMemcpyAsync(raw, p->d_text_blobs, (size_t)p->text_raw_total, hipMemcpyDeviceToHost, st));
   if (p->text_pests_total)
     PLAN_TRY(hipMemcpyAsync(pests, p->d_text_blobs + p->text_pests_at, (size_t)p->text_pests_total, hipMemcpyDeviceToHost, st));
+  PLAN_TRY(pgpu_ctx_wait(ctx));
+  PLAN_TRY(hipGetLastError());
+  return PGPU_OK;
+}
+
+// ---- the records of the units of the last run_units to est-fact's three side files, where they lie (pgpu_side.hip) -------
+extern "C" int pgpu_pairing_plan_run_sides(pgpu_ctx* ctx, pgpu_pairing_plan* p) {
+  if (!ctx || !p) return PGPU_EINVAL;
+  p->side_total[0] = p->side_total[1] = p->side_total[2] = 0; p->side_ms = p->side_write_ms = 0.f; p->side_timed = false;
+  lower(p, TEXTS);
+  if (p->stage < TEXTS) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_sides needs the headers of pgpu_pairing_plan_run_texts");
+  const size_t n_units = p->n_units;
+  if (p->n_pat == 0 || n_units == 0) return reached(p, SIDES);
+  if (const int rc = still_owns(ctx, p, "texts")) return rc;
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  const ProfRange range("sides");
+  const SideLayout L = side_layout(n_units, pgpu_scan_tmp_bytes(n_units + 1));
+  PLAN_NEED(p->d_side = stage_block(p, p->d_side, &p->side_cap, L.total, SLOT_SIDES));
+  PLAN_TRY(plan_events(p, EV_SIDES, 3));
+  const UnitLayout U = unit_layout(n_units, (size_t)p->final_total, pgpu_scan_tmp_bytes(n_units + 1));
+  const TextLayout T = text_layout(n_units, p->text_headers_len, pgpu_scan_tmp_bytes(n_units + 1));
+  pgpu_side_job job;
+  job.q = (const pgpu_unit_query*)(p->d_unit + U.q); job.units = (const pgpu_unit_result*)(p->d_unit + U.out); job.n = (uint32_t)n_units;
+  job.recs = p->d_meg_out; job.recs_len = p->meg_total; job.rec_first = p->d_meg_off; job.n_pat = (uint32_t)p->n_pat;
+  job.hdr = p->d_text + T.hdr; job.hdr_first = (const unsigned long long*)(p->d_text + T.hdr_first);
+  job.seqs = p->d_pats; job.seq_at = p->d_orig_off; job.seq_off = p->d_pat_off;
+  job.block = p->d_side;
+  for (int k = 0; k < 3; ++k) job.ev[k] = p->ev[EV_SIDES + k];
+  PLAN_TRY(pgpu_side_count(ctx, job));                 // the call's one host wait
+  const SideBlobs S = side_blobs(job.total);
+  PLAN_NEED(p->d_side_blobs = stage_block(p, p->d_side_blobs, &p->side_blobs_cap, S.total, SLOT_SIDE_BLOBS));
+  PLAN_TRY(pgpu_side_write(ctx, job, p->d_side_blobs + S.at[0], p->d_side_blobs + S.at[1], p->d_side_blobs + S.at[2]));
+  for (int k = 0; k < 3; ++k) p->side_total[k] = job.total[k];
+  p->side_timed = p->ev[EV_SIDES] != nullptr;
+  return reached(p, SIDES);
+}
+
+extern "C" uint64_t pgpu_pairing_plan_side_bytes(const pgpu_pairing_plan* p, int which) {
+  return (p && which >= 0 && which < 3) ? p->side_total[which] : 0;
+}
+// the run did not wait for its write pass: the first question about its time does
+static void side_times(pgpu_pairing_plan* p) {
+  if (!p->side_timed || p->stage < SIDES) return;
+  p->side_timed = false;
+  if (hipEventSynchronize(p->ev[EV_SIDES + 1]) != hipSuccess) return;
+  elapsed_pairs(p, EV_SIDES, 1, &p->side_ms);
+  hipEventElapsedTime(&p->side_write_ms, p->ev[EV_SIDES + 2], p->ev[EV_SIDES + 1]);
+}
+extern "C" double pgpu_pairing_plan_sides_ms(pgpu_pairing_plan* p) {
+  if (!p) return 0.0;
+  side_times(p);
+  return p->side_ms;
+}
+extern "C" double pgpu_pairing_plan_sides_write_ms(pgpu_pairing_plan* p) {
+  if (!p) return 0.0;
+  side_times(p);
+  return p->side_write_ms;
+}
+
+extern "C" int pgpu_pairing_plan_fetch_sides(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_side_result* out, void* megs, size_t megs_cap,
+                                             void* pmegs, size_t pmegs_cap, void* edges, size_t edges_cap) {
+  if (!ctx || !p || (megs_cap && !megs) || (pmegs_cap && !pmegs) || (edges_cap && !edges)) return PGPU_EINVAL;
+  if (p->stage < SIDES) return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_sides needs pgpu_pairing_plan_run_sides first");
+  if (p->n_pat && p->n_units && !out) return PGPU_EINVAL;
+  if (const int rc = still_owns(ctx, p, "results")) return rc;
+  if (megs_cap < p->side_total[0] || pmegs_cap < p->side_total[1] || edges_cap < p->side_total[2])
+    return pgpu_ctx_fail(ctx, PGPU_ENOSPC, SIDE_NO_SPACE);
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_pat == 0 || p->n_units == 0) return PGPU_OK;
+  const SideLayout L = side_layout(p->n_units, pgpu_scan_tmp_bytes(p->n_units + 1));
+  const SideBlobs S = side_blobs(p->side_total);
+  PLAN_TRY(hipMemcpyAsync(out, p->d_side + L.out, p->n_units * sizeof(pgpu_side_result), hipMemcpyDeviceToHost, st));
+  void* const dst[3] = { megs, pmegs, edges };
+  for (int k = 0; k < 3; ++k)
+    if (p->side_total[k]) PLAN_TRY(hipMemcpyAsync(dst[k], p->d_side_blobs + S.at[k], (size_t)p->side_total[k], hipMemcpyDeviceToHost, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   PLAN_TRY(hipGetLastError());
   return PGPU_OK;

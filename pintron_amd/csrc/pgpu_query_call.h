@@ -1,7 +1,7 @@
 // The host side of a query on the resident index, once: what the nine entries pgpu_index_find, pgpu_index_classify,
 // pgpu_index_small_exons, pgpu_index_refine_introns, pgpu_index_refine_chains, pgpu_index_clean_chains,
 // pgpu_index_gap_chains, pgpu_index_tail_chains and pgpu_index_small_chains, the index forms of the four device stages
-// (pgpu_index_candidates, pgpu_index_factorizations, pgpu_index_final_factorizations, pgpu_unit_records), pgpu_unit_texts and
+// (pgpu_index_candidates, pgpu_index_factorizations, pgpu_index_final_factorizations, pgpu_unit_records), pgpu_unit_texts, pgpu_unit_sides and
 // pgpu_final_handoffs_probe share around their kernels.  An entry validates, lays out its device block, copies in, launches,
 // copies out and waits, as straight-line code; the QueryCall on its stack owns what has to be given back whichever way the
 // entry returns.  The five chained entries (one query = one list of exons, chained on the device) share more: the chained

@@ -1,5 +1,5 @@
 // What the drives of the device stages share (pgpu_fact_drive, pgpu_final_drive, pgpu_unit_drive, pgpu_text_count,
-// pgpu_index_candidates, the plan's scan_total): DRIVE inside a function that returns hipError_t, and the compact tail.  Internal; host code only.
+// pgpu_side_count, pgpu_index_candidates, the plan's scan_total): DRIVE inside a function that returns hipError_t, and the compact tail.  Internal; host code only.
 #pragma once
 #include "pgpu_index.h"
 

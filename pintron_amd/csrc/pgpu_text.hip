@@ -13,7 +13,7 @@
 //                       separators in bytes (at most 50), and the wave then copies the stretches together, one after the
 //                       other -- E and X of every exon, H per factorization, H and S of the pests entry -- through
 //                       wave_copy.
-//   wave_copy           destination-aligned 4-byte stores by consecutive lanes; a source word is two aligned loads combined
+//   wave_copy           (pgpu_wave_copy.h, shared with pgpu_side.hip) destination-aligned 4-byte stores by consecutive lanes; a source word is two aligned loads combined
 //                       across the misalignment (__builtin_amdgcn_alignbyte), one when source and destination agree mod 4;
 //                       single bytes only at the two edges (at most 3 each).  An aligned load may read up to 3 bytes before
 //                       and past a stretch: headers, sequences and genomic lie in allocations whose base is a multiple of
@@ -27,6 +27,7 @@
 #include "pgpu_query_call.h"
 #include "pgpu_stage_drive.h"
 #include "pgpu_text.h"
+#include "pgpu_wave_copy.h"
 
 namespace {
 
@@ -127,24 +128,6 @@ void text_count_kernel(const TextIn in, pgpu_text_result* __restrict__ out, uint
   out[u] = r;
   raw_counts[u] = r.raw_bytes;
   pests_counts[u] = r.pests_bytes;
-}
-
-// dst[0 .. n) = src[0 .. n), by the whole wave; every argument is the same in all lanes
-__device__ __forceinline__ void wave_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t n, uint32_t lane) {
-  uint32_t head = (uint32_t)(0u - (uint32_t)(uintptr_t)dst) & 3u;
-  if (head > n) head = n;
-  if (lane < head) dst[lane] = src[lane];
-  const uint32_t body = n - head, n_words = body >> 2, tail = body & 3u;
-  uint32_t* __restrict__ const dw = (uint32_t*)(dst + head);
-  const uint8_t* const s = src + head;
-  const uint32_t sa = (uint32_t)(uintptr_t)s & 3u;
-  const uint32_t* __restrict__ const sw = (const uint32_t*)(s - sa);
-  if (sa == 0) {
-    for (uint32_t i = lane; i < n_words; i += 64) dw[i] = sw[i];
-  } else {
-    for (uint32_t i = lane; i < n_words; i += 64) dw[i] = __builtin_amdgcn_alignbyte(sw[i + 1], sw[i], sa);
-  }
-  if (lane < tail) dst[head + 4 * n_words + lane] = src[head + 4 * n_words + lane];
 }
 
 // lane k's value in every lane (k the same in all lanes)
