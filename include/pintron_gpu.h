@@ -445,6 +445,7 @@ double pgpu_index_gap_chains_kernel_ms(void);
 #define PGPU_TAIL_MAX_AFFIX        256   /* EST bytes of a lost prefix / suffix window whose DP has to run; beyond: same */
 #define PGPU_TAIL_MAX_SMALL_WINDOW 128   /* EST bytes of the BORDERS pattern of a small-exon analysis; beyond: same */
 #define PGPU_TAIL_MAX_SMALL_GEN    256   /* genomic bytes of an analysed exon whose edit distance has to run; beyond: same */
+#define PGPU_TAIL_WIDE_MAX_AFFIX  1024   /* the same window in pgpu_index_tail_chains_wide: sixteen rows of the DP per lane */
 #define PGPU_TAIL_UB_MED_EXON      100   /* _UB_MED_EXON_: a longer exon (on the EST) is not analysed in step 5 */
 #define PGPU_TAIL_AFFIXES_LENGTH     5   /* _AFFIXES_LENGTH_: what step 5 takes of the two neighbours */
 typedef struct {
@@ -533,6 +534,15 @@ int pgpu_index_tail_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* est
 /* HIP-event time of the kernel of the calling thread's last pgpu_index_tail_chains on a context with timing on
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_tail_chains_kernel_ms(void);
+/* The same entry with one cap lifted: an affix window of up to PGPU_TAIL_WIDE_MAX_AFFIX EST bytes (a prefix's genomic
+ * window is then at most (int)(1.17 * 1024) = 1198 bytes).  Signature, validation, layouts, every other cap and every
+ * refusal are pgpu_index_tail_chains'.  The answer equals that entry's, byte for byte, wherever that entry answers: the
+ * call runs its kernel first, then a second kernel over the same arrays that takes only the queries left at PGPU_ERANGE
+ * and answers them from the input again; one that meets another cap stays PGPU_ERANGE.
+ * pgpu_index_tail_chains_kernel_ms reports this call too: both kernels, one event pair. */
+int pgpu_index_tail_chains_wide(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                const pgpu_factor* exons, size_t n_exons_total, const pgpu_tail_query* q, size_t n,
+                                pgpu_factor* out_exons, uint8_t* out_steps, pgpu_tail_result* out);
 
 /* The last two routines of refine_EST_factorizations (src/factorization-refinement.c:1270-1305) that concern one
  * factorization alone, chained: search_for_new_small_exons (:875-912, with search_small_exon_at_prefix :500-606 and
@@ -545,6 +555,7 @@ double pgpu_index_tail_chains_kernel_ms(void);
 #define PGPU_SMALL_MAX_PREFIX_WINDOW 256   /* rows (EST bytes, allelen) of the prefix search's BORDERS: lev_wave_body<4,
                                               BORDERS>, four rows per lane; small_kernel has no scratch and no spilled
                                               vector register with it */
+#define PGPU_SMALL_WIDE_MAX_PREFIX_WINDOW 1024   /* the same rows in pgpu_index_small_chains_wide: sixteen per lane */
 #define PGPU_SMALL_MAX_KBAND          31   /* as step 5 of pgpu_index_clean_chains: a genomic exon length above 1 033 */
 typedef pgpu_tail_query pgpu_small_query;      /* est_off = the WORKING sequence (steps 1-2), orig_off = the ORIGINAL (step 3) */
 typedef struct { int32_t min_intron_length; uint32_t reserved; } pgpu_small_params;   /* 8 bytes; config->min_intron_length, any value */
@@ -625,6 +636,17 @@ int pgpu_index_small_chains(pgpu_ctx* ctx, const pgpu_index* idx, const char* es
 /* HIP-event time of the kernel of the calling thread's last pgpu_index_small_chains on a context with timing on
  * (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_small_chains_kernel_ms(void);
+/* The same entry with one cap lifted: step 1's border refinement takes an allelen of up to
+ * PGPU_SMALL_WIDE_MAX_PREFIX_WINDOW.  Signature, validation, layouts, every other cap and every refusal are
+ * pgpu_index_small_chains'.  The answer equals that entry's, byte for byte, wherever that entry answers: the call runs
+ * its kernel first, then a second kernel over the same arrays that takes only the queries with refused == 2 and answers
+ * them from the input again; one that then meets another cap is refused with that cap's code, and an allelen beyond the
+ * wide cap stays refused == 2.  pgpu_index_small_chains_kernel_ms reports this call too: both kernels, one event pair. */
+int pgpu_index_small_chains_wide(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                 const pgpu_factor* exons, size_t n_exons_total, const pgpu_small_query* q, size_t n,
+                                 const pgpu_small_params* params,
+                                 pgpu_factor* out_exons /* 2 * n_exons_total */, uint8_t* out_steps /* 2 * n_exons_total */,
+                                 pgpu_small_result* out);
 
 /* ------------------------------------------------------------------------------------------ */
 /* pairings -- replaces build_vertex_set (src/max-emb-graph.c:218-392): for every position p   */
@@ -971,6 +993,11 @@ int pgpu_pairing_plan_create_with_originals(pgpu_ctx* ctx, const pgpu_index* idx
  * the run.  params == NULL is a bare PGPU_EINVAL.  An empty plan is PGPU_OK.  A rerun gives the same bytes.  The buffers
  * come from where the MEG stage's do.  The one host wait of the call is its last statement (8 bytes: the exon count). */
 int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_small_params* params);
+/* The same run with stages 4 and 5 as pgpu_index_tail_chains_wide and pgpu_index_small_chains_wide answer them: the same
+ * fifth stage by the same rules, fetched with pgpu_pairing_plan_fetch_final_factorizations, and the stages above it run
+ * on what it leaves.  The results equal the narrow run's except where that one is HOST at stage 4 or 5 with detail 1 for
+ * a window the wide caps take.  pgpu_pairing_plan_final_ms reports it: the wide kernels inside the pairs k = 1 and 2. */
+int pgpu_pairing_plan_run_final_factorizations_wide(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_small_params* params);
 uint64_t pgpu_pairing_plan_final_exons(const pgpu_pairing_plan* plan);   /* exons of the last run_final_factorizations */
 /* out: n_pat results; exons, steps: at least final_exons entries (PGPU_ENOSPC when cap is smaller) */
 int pgpu_pairing_plan_fetch_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_final_result* out,
@@ -996,6 +1023,13 @@ int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const 
 /* HIP-event time of the whole device part (both drivers) of the calling thread's last pgpu_index_final_factorizations on
  * a context with timing on (as pgpu_index_find_kernel_ms); 0 without timing */
 double pgpu_index_final_factorizations_kernel_ms(void);
+/* pgpu_index_final_factorizations with stages 4 and 5 as the two wide chained entries answer them; everything else, the
+ * _kernel_ms getter included, is that entry's */
+int pgpu_index_final_factorizations_wide(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                         const pgpu_factor* exons, size_t n_exons_total, const pgpu_final_query* q, size_t n,
+                                         const pgpu_fact_params* params, const pgpu_small_params* small_params,
+                                         pgpu_final_result* out, pgpu_factor* out_exons, uint8_t* out_steps, size_t cap,
+                                         size_t* n_out);
 
 /* ------------------------------------------------------------------------------------------ */
 /* units -- from the finals of the patterns to est-fact's answer per INPUT EST: a unit is an   */

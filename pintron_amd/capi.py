@@ -276,6 +276,8 @@ EXPORTS = [
     "pgpu_index_gap_chains", "pgpu_index_gap_chains_kernel_ms",
     "pgpu_index_tail_chains", "pgpu_index_tail_chains_kernel_ms",
     "pgpu_index_small_chains", "pgpu_index_small_chains_kernel_ms",
+    "pgpu_index_tail_chains_wide", "pgpu_index_small_chains_wide",
+    "pgpu_index_final_factorizations_wide", "pgpu_pairing_plan_run_final_factorizations_wide",
     "pgpu_pairing_plan_create", "pgpu_pairing_plan_create_resident", "pgpu_pairing_plan_run", "pgpu_pairing_plan_count",
     "pgpu_pairing_plan_positions", "pgpu_pairing_plan_kernel_ms", "pgpu_pairing_plan_fetch",
     "pgpu_pairing_plan_destroy",
@@ -364,11 +366,13 @@ def lib():
         L.pgpu_index_gap_chains_kernel_ms.restype = C.c_double
         L.pgpu_index_tail_chains.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(TailQuery), sz,
                                              C.POINTER(Factor), C.POINTER(C.c_uint8), C.POINTER(TailResult)]
+        L.pgpu_index_tail_chains_wide.argtypes = L.pgpu_index_tail_chains.argtypes
         L.pgpu_index_tail_chains_kernel_ms.argtypes = []
         L.pgpu_index_tail_chains_kernel_ms.restype = C.c_double
         L.pgpu_index_small_chains.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(SmallQuery), sz,
                                               C.POINTER(SmallParams), C.POINTER(Factor), C.POINTER(C.c_uint8),
                                               C.POINTER(SmallResult)]
+        L.pgpu_index_small_chains_wide.argtypes = L.pgpu_index_small_chains.argtypes
         L.pgpu_index_small_chains_kernel_ms.argtypes = []
         L.pgpu_index_small_chains_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_meg.argtypes = [vp, vp, vp]
@@ -402,6 +406,7 @@ def lib():
         L.pgpu_pairing_plan_create_with_originals.argtypes = [vp, vp, C.c_char_p, C.POINTER(u64), sz, C.c_int,
                                                               C.POINTER(C.c_uint32), C.POINTER(u64), C.c_char_p, sz, C.POINTER(vp)]
         L.pgpu_pairing_plan_run_final_factorizations.argtypes = [vp, vp, C.POINTER(SmallParams)]
+        L.pgpu_pairing_plan_run_final_factorizations_wide.argtypes = [vp, vp, C.POINTER(SmallParams)]
         L.pgpu_pairing_plan_final_exons.argtypes = [vp]
         L.pgpu_pairing_plan_final_exons.restype = u64
         L.pgpu_pairing_plan_fetch_final_factorizations.argtypes = [vp, vp, C.POINTER(FinalResult), C.POINTER(Factor),
@@ -411,6 +416,7 @@ def lib():
         L.pgpu_index_final_factorizations.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(Factor), sz, C.POINTER(FinalQuery), sz,
                                                       C.POINTER(FactParams), C.POINTER(SmallParams), C.POINTER(FinalResult),
                                                       C.POINTER(Factor), C.POINTER(C.c_uint8), sz, C.POINTER(sz)]
+        L.pgpu_index_final_factorizations_wide.argtypes = L.pgpu_index_final_factorizations.argtypes
         L.pgpu_index_final_factorizations_kernel_ms.argtypes = []
         L.pgpu_index_final_factorizations_kernel_ms.restype = C.c_double
         L.pgpu_unit_records.argtypes = [vp, C.POINTER(FinalResult), sz, C.POINTER(Factor), sz, C.POINTER(C.c_uint8),
@@ -718,17 +724,19 @@ class Index:
     def gap_chains_kernel_ms(self):
         return self.ctx.L.pgpu_index_gap_chains_kernel_ms()
 
-    def tail_chains_raw(self, ests: bytes, exons, queries, n: int):
-        """One pgpu_index_tail_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
-        TAIL_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of TAIL_RESULT_DTYPE)."""
-        return self._chained_raw(self.ctx.L.pgpu_index_tail_chains, TailQuery, TailResult, TAIL_RESULT_DTYPE,
+    def tail_chains_raw(self, ests: bytes, exons, queries, n: int, wide: bool = False):
+        """One pgpu_index_tail_chains call as it is (wide: pgpu_index_tail_chains_wide): `exons` a numpy array of
+        FACTOR_DTYPE, `queries` one of TAIL_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of
+        TAIL_RESULT_DTYPE)."""
+        fn = self.ctx.L.pgpu_index_tail_chains_wide if wide else self.ctx.L.pgpu_index_tail_chains
+        return self._chained_raw(fn, TailQuery, TailResult, TAIL_RESULT_DTYPE,
                                  ests, exons, queries, n)
 
-    def tail_chains(self, ests: bytes, exons, queries):
+    def tail_chains(self, ests: bytes, exons, queries, wide: bool = False):
         """What est-fact does to every factorization `queries` names directly behind the refinement loop (tail correction,
         polyA, validity, lost prefix and suffix, false small exons, chained on the device): (out_exons, out_steps,
-        results) as numpy arrays."""
-        rc, out_exons, out_steps, res = self.tail_chains_raw(ests, exons, queries, len(queries))
+        results) as numpy arrays.  wide: lost windows of up to 1024 EST bytes (pgpu_index_tail_chains_wide)."""
+        rc, out_exons, out_steps, res = self.tail_chains_raw(ests, exons, queries, len(queries), wide)
         self.ctx.check(rc)
         return out_exons, out_steps, res
 
@@ -736,8 +744,8 @@ class Index:
         return self.ctx.L.pgpu_index_tail_chains_kernel_ms()
 
     def small_chains_raw(self, ests: bytes, exons, queries, n: int, min_intron_length: int, params_reserved: int = 0,
-                         no_params: bool = False):
-        """One pgpu_index_small_chains call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+                         no_params: bool = False, wide: bool = False):
+        """One pgpu_index_small_chains call as it is (wide: pgpu_index_small_chains_wide): `exons` a numpy array of FACTOR_DTYPE, `queries` one of
         SMALL_QUERY_DTYPE.  Returns (rc, out_exons, out_steps, results as a numpy array of SMALL_RESULT_DTYPE); the two
         output arrays have 2 * len(exons) entries, a query's list at 2 * first_exon."""
         import numpy as np
@@ -745,19 +753,20 @@ class Index:
         out_steps = np.zeros(2 * len(exons), dtype=np.uint8)
         res = np.zeros(n, dtype=np.dtype(SMALL_RESULT_DTYPE))
         prm = SmallParams(min_intron_length, params_reserved)
-        rc = self.ctx.L.pgpu_index_small_chains(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)),
-                                                len(exons), queries.ctypes.data_as(C.POINTER(SmallQuery)), n,
-                                                None if no_params else C.byref(prm),
-                                                out_exons.ctypes.data_as(C.POINTER(Factor)),
-                                                out_steps.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                res.ctypes.data_as(C.POINTER(SmallResult)))
+        fn = self.ctx.L.pgpu_index_small_chains_wide if wide else self.ctx.L.pgpu_index_small_chains
+        rc = fn(self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)),
+                len(exons), queries.ctypes.data_as(C.POINTER(SmallQuery)), n,
+                None if no_params else C.byref(prm),
+                out_exons.ctypes.data_as(C.POINTER(Factor)),
+                out_steps.ctypes.data_as(C.POINTER(C.c_uint8)),
+                res.ctypes.data_as(C.POINTER(SmallResult)))
         return rc, out_exons, out_steps, res
 
-    def small_chains(self, ests: bytes, exons, queries, min_intron_length: int):
+    def small_chains(self, ests: bytes, exons, queries, min_intron_length: int, wide: bool = False):
         """The last steps of the reference's refine_EST_factorizations over every factorization `queries` names (a new small
         exon in front of the first exon and between every two, then the last cleaning on the original sequence, chained on
         the device): (out_exons, out_steps, results) as numpy arrays, the first two of 2 * len(exons) entries."""
-        rc, out_exons, out_steps, res = self.small_chains_raw(ests, exons, queries, len(queries), min_intron_length)
+        rc, out_exons, out_steps, res = self.small_chains_raw(ests, exons, queries, len(queries), min_intron_length, wide=wide)
         self.ctx.check(rc)
         return out_exons, out_steps, res
 
@@ -821,8 +830,8 @@ class Index:
     def factorizations_kernel_ms(self):
         return self.ctx.L.pgpu_index_factorizations_kernel_ms()
 
-    def final_factorizations_raw(self, ests: bytes, exons, queries, n: int, params, small_params, cap: int):
-        """One pgpu_index_final_factorizations call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
+    def final_factorizations_raw(self, ests: bytes, exons, queries, n: int, params, small_params, cap: int, wide: bool = False):
+        """One pgpu_index_final_factorizations call as it is (wide: pgpu_index_final_factorizations_wide): `exons` a numpy array of FACTOR_DTYPE, `queries` one of
         FINAL_QUERY_DTYPE, `params` a FactParams, `small_params` a SmallParams or None.  Returns (rc, results as a numpy array
         of FINAL_RESULT_DTYPE, exons and step bytes (cap entries each), n_out)."""
         import numpy as np
@@ -830,7 +839,8 @@ class Index:
         out_exons = np.zeros(cap, dtype=np.dtype(FACTOR_DTYPE))
         out_steps = np.zeros(cap, dtype=np.uint8)
         total = C.c_size_t(0)
-        rc = self.ctx.L.pgpu_index_final_factorizations(
+        fn = self.ctx.L.pgpu_index_final_factorizations_wide if wide else self.ctx.L.pgpu_index_final_factorizations
+        rc = fn(
             self.ctx.h, self.h, ests, len(ests), exons.ctypes.data_as(C.POINTER(Factor)), len(exons),
             queries.ctypes.data_as(C.POINTER(FinalQuery)), n, C.byref(params),
             None if small_params is None else C.byref(small_params), res.ctypes.data_as(C.POINTER(FinalResult)),
@@ -838,13 +848,14 @@ class Index:
         return rc, res, out_exons, out_steps, total.value
 
     def final_factorizations(self, ests: bytes, exons, queries, complexity_threshold=20.0, suffpref_length_on_est=30,
-                             suffpref_length_for_intron=70, suffpref_length_on_gen=30, min_intron_length=40):
+                             suffpref_length_for_intron=70, suffpref_length_on_gen=30, min_intron_length=40, wide=False):
         """Every candidate `queries` names through clean, gaps, refine, tail and small in one call (n_exons == 0: no
         candidate): (results as a numpy array of FINAL_RESULT_DTYPE, the final exons, compact, and their step bytes)."""
         prm = FactParams(complexity_threshold, suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen,
                          min_intron_length)
         rc, res, out_exons, out_steps, total = self.final_factorizations_raw(ests, exons, queries, len(queries), prm,
-                                                                             SmallParams(min_intron_length, 0), 2 * len(exons))
+                                                                             SmallParams(min_intron_length, 0), 2 * len(exons),
+                                                                             wide)
         self.ctx.check(rc)
         return res, out_exons[:total], out_steps[:total]
 
@@ -1148,14 +1159,16 @@ class PairingPlan:
         """HIP-event time of the last run_factorizations: k = 0 the whole call, 1 clean, 2 gaps, 3 refine"""
         return self.ctx.L.pgpu_pairing_plan_factorizations_ms(self.h, k)
 
-    def run_final_factorizations_raw(self, min_intron_length=40, reserved=0, no_params=False):
+    def run_final_factorizations_raw(self, min_intron_length=40, reserved=0, no_params=False, wide=False):
         prm = SmallParams(min_intron_length, reserved)
-        return self.ctx.L.pgpu_pairing_plan_run_final_factorizations(self.ctx.h, self.h, None if no_params else C.byref(prm))
+        L = self.ctx.L
+        fn = L.pgpu_pairing_plan_run_final_factorizations_wide if wide else L.pgpu_pairing_plan_run_final_factorizations
+        return fn(self.ctx.h, self.h, None if no_params else C.byref(prm))
 
-    def run_final_factorizations(self, min_intron_length=40):
-        """every factorization of the last run_factorizations through tail and small, where it lies; returns the number of
-        exons of the answer"""
-        self.ctx.check(self.run_final_factorizations_raw(min_intron_length))
+    def run_final_factorizations(self, min_intron_length=40, wide=False):
+        """every factorization of the last run_factorizations through tail and small, where it lies (wide: with the wide
+        kernels behind the two stage kernels); returns the number of exons of the answer"""
+        self.ctx.check(self.run_final_factorizations_raw(min_intron_length, wide=wide))
         return self.ctx.L.pgpu_pairing_plan_final_exons(self.h)
 
     def fetch_final_factorizations_raw(self, cap=None):

@@ -189,7 +189,7 @@ hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& d) {
     DRIVE(hipMemcpyAsync(tr, d.given_tail->results, n * sizeof *tr, hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(ex_tout, d.given_tail->exons, ((size_t)E + n) * sizeof(pgpu_factor), hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(B + L.tsteps, d.given_tail->steps, (size_t)E + n, hipMemcpyHostToDevice, st));
-  } else pgpu_tail_launch(d.ix.T, tlen, d.ests, ex_tin, tq, n, waves, ex_tout, B + L.tsteps, tr, st);
+  } else (d.wide ? pgpu_tail_wide_launch : pgpu_tail_launch)(d.ix.T, tlen, d.ests, ex_tin, tq, n, waves, ex_tout, B + L.tsteps, tr, st);
   DRIVE(drive_record(d.ev, 3, st));
   hipLaunchKernelGGL(final_tail_to_small_kernel, grid, blk, 0, st, tq, tr, n, E, d.ests_len, tlen, ex_tout, B + L.tsteps, ex_sin, sq, res);
   DRIVE(drive_record(d.ev, 4, st));
@@ -197,7 +197,7 @@ hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& d) {
     DRIVE(hipMemcpyAsync(sr, d.given_small->results, n * sizeof *sr, hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(ex_sout, d.given_small->exons, 2 * ((size_t)E + n) * sizeof(pgpu_factor), hipMemcpyHostToDevice, st));
     DRIVE(hipMemcpyAsync(B + L.ssteps, d.given_small->steps, 2 * ((size_t)E + n), hipMemcpyHostToDevice, st));
-  } else pgpu_small_launch(d.ix, *d.cv, d.ests, ex_sin, sq, n, d.min_intron_length, waves, ex_sout, B + L.ssteps, sr, st);
+  } else (d.wide ? pgpu_small_wide_launch : pgpu_small_launch)(d.ix, *d.cv, d.ests, ex_sin, sq, n, d.min_intron_length, waves, ex_sout, B + L.ssteps, sr, st);
   DRIVE(drive_record(d.ev, 5, st));
   hipLaunchKernelGGL(final_gather_kernel<false>, grid, blk, 0, st, sq, sr, n, res, counts, (const unsigned long long*)nullptr,
                      (const pgpu_factor*)nullptr, (const uint8_t*)nullptr, (pgpu_factor*)nullptr, (uint8_t*)nullptr);
@@ -210,11 +210,11 @@ hipError_t pgpu_final_drive(pgpu_ctx* ctx, pgpu_final_job& d) {
 
 extern "C" double pgpu_index_final_factorizations_kernel_ms(void) { return t_final_ms; }
 
-extern "C" int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
-                                               const pgpu_factor* exons, size_t n_exons_total, const pgpu_final_query* q, size_t n,
-                                               const pgpu_fact_params* params, const pgpu_small_params* small_params,
-                                               pgpu_final_result* out, pgpu_factor* out_exons, uint8_t* out_steps, size_t cap,
-                                               size_t* n_out) {
+// the entry in its two forms: `wide` is pgpu_final_job's
+static int final_factorizations_call(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len, const pgpu_factor* exons,
+                                     size_t n_exons_total, const pgpu_final_query* q, size_t n, const pgpu_fact_params* params,
+                                     const pgpu_small_params* small_params, pgpu_final_result* out, pgpu_factor* out_exons,
+                                     uint8_t* out_steps, size_t cap, size_t* n_out, const bool wide) {
   t_final_ms = 0.0;      // a refused call has no kernel time either (include/pintron_gpu.h: "the last call")
   static_assert(sizeof(pgpu_final_query) == 32 && sizeof(pgpu_final_result) == 32 && sizeof(pgpu_small_params) == 8, "ABI layout");
   if (!ctx || !idx || !params || !small_params || !n_out || (n && (!q || !out)) || (ests_len && !ests) ||
@@ -258,7 +258,7 @@ extern "C" int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* 
   fin.ests = call.d; fin.ests_len = ests_len;
   fin.fq = (const pgpu_final_query*)(call.d + o_q); fin.pat_off = nullptr; fin.orig_off = nullptr;
   fin.n = (uint32_t)n; fin.n_exons_total = (uint32_t)n_exons_total; fin.min_intron_length = small_params->min_intron_length;
-  fin.fact_block = job.block; fin.block = call.d + o_final;
+  fin.fact_block = job.block; fin.block = call.d + o_final; fin.wide = wide;
   for (int k = 0; k < 6; ++k) fin.ev[k] = call.ev[8 + k];
   TRY_HIP(pgpu_final_drive(ctx, fin));
   *n_out = (size_t)fin.total;
@@ -267,6 +267,24 @@ extern "C" int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* 
   TRY_HIP(pgpu_ctx_wait(ctx));
   if (call.ev[0]) { float ms = 0.f; (void)hipEventElapsedTime(&ms, call.ev[0], call.ev[9]); t_final_ms = ms; }
   return PGPU_OK;
+}
+
+extern "C" int pgpu_index_final_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                               const pgpu_factor* exons, size_t n_exons_total, const pgpu_final_query* q, size_t n,
+                                               const pgpu_fact_params* params, const pgpu_small_params* small_params,
+                                               pgpu_final_result* out, pgpu_factor* out_exons, uint8_t* out_steps, size_t cap,
+                                               size_t* n_out) {
+  return final_factorizations_call(ctx, idx, ests, ests_len, exons, n_exons_total, q, n, params, small_params, out, out_exons,
+                                   out_steps, cap, n_out, false);
+}
+
+extern "C" int pgpu_index_final_factorizations_wide(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                                    const pgpu_factor* exons, size_t n_exons_total, const pgpu_final_query* q,
+                                                    size_t n, const pgpu_fact_params* params, const pgpu_small_params* small_params,
+                                                    pgpu_final_result* out, pgpu_factor* out_exons, uint8_t* out_steps, size_t cap,
+                                                    size_t* n_out) {
+  return final_factorizations_call(ctx, idx, ests, ests_len, exons, n_exons_total, q, n, params, small_params, out, out_exons,
+                                   out_steps, cap, n_out, true);
 }
 
 // ---- the hand-off kernels alone, for the tests (declared nowhere in include/pintron_gpu.h) ----------------------------

@@ -174,6 +174,9 @@ struct pgpu_final_job {
   uint8_t* block;
   hipEvent_t ev[6];            // null without timing: 0-1 the whole drive, 2-3 tail_kernel, 4-5 small_kernel
   unsigned long long total;
+  // the wide form: tail_wide_kernel and small_wide_kernel are queued behind the two stage kernels (pgpu_tail_wide_launch,
+  // pgpu_small_wide_launch), inside the event pairs 2-3 and 4-5
+  bool wide = false;
   // Null in every call of the library.  pgpu_final_handoffs_probe sets both: host arrays in the layout of the block's
   // tr / ex_tout / tsteps and sr / ex_sout / ssteps that are copied in where the stage kernel would have written them, and
   // the kernel is not launched -- the hand-off kernels then run over results no input brings through the stages.

@@ -882,7 +882,7 @@ extern "C" int pgpu_pairing_plan_fetch_factorizations(pgpu_ctx* ctx, pgpu_pairin
 }
 
 // ---- the factorizations of the last run_factorizations through tail and small, where they lie (pgpu_final.hip) --------
-extern "C" int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_small_params* prm) {
+static int run_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_small_params* prm, const bool wide) {
   if (!ctx || !p || !prm) return PGPU_EINVAL;
   p->final_total = 0;
   for (auto& m : p->final_ms) m = 0.f;
@@ -904,12 +904,20 @@ extern "C" int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pa
   job.ests = p->d_pats; job.ests_len = p->seq_bytes;
   job.fq = nullptr; job.pat_off = p->d_pat_off; job.orig_off = p->d_orig_off;
   job.n = (uint32_t)p->n_pat; job.n_exons_total = (uint32_t)p->cand_total; job.min_intron_length = prm->min_intron_length;
-  job.fact_block = p->d_fact; job.block = p->d_final;
+  job.fact_block = p->d_fact; job.block = p->d_final; job.wide = wide;
   for (int k = 0; k < 6; ++k) job.ev[k] = p->ev[EV_FINAL + k];
   PLAN_TRY(pgpu_final_drive(ctx, job));
   p->final_total = job.total;
   elapsed_pairs(p, EV_FINAL, 3, p->final_ms);
   return reached(p, FINALS);
+}
+
+extern "C" int pgpu_pairing_plan_run_final_factorizations(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_small_params* prm) {
+  return run_final_factorizations(ctx, p, prm, false);
+}
+// the same rung with the wide kernels behind the two stage kernels (pgpu_final_job::wide)
+extern "C" int pgpu_pairing_plan_run_final_factorizations_wide(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_small_params* prm) {
+  return run_final_factorizations(ctx, p, prm, true);
 }
 
 extern "C" uint64_t pgpu_pairing_plan_final_exons(const pgpu_pairing_plan* p) { return p ? p->final_total : 0; }

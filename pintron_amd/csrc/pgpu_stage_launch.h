@@ -83,3 +83,10 @@ void pgpu_tail_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, cons
 void pgpu_small_launch(const LcfIndexView& ix, const ClassView& cv, const uint8_t* ests, const pgpu_factor* exons,
                        const pgpu_small_query* q, uint32_t n, int min_intron_length, size_t waves, pgpu_factor* out_exons,
                        uint8_t* out_steps, pgpu_small_result* out, hipStream_t st);
+// pgpu_tail_wide.hip, pgpu_small_wide.hip: the narrow launch above, then the wide kernel over the same arrays on the same
+// stream for the queries the narrow one refused for a window (tail: PGPU_ERANGE; small: refused == 2); the same `waves`
+void pgpu_tail_wide_launch(const uint8_t* T, uint32_t tlen, const uint8_t* ests, const pgpu_factor* exons, const pgpu_tail_query* q,
+                           uint32_t n, size_t waves, pgpu_factor* out_exons, uint8_t* out_steps, pgpu_tail_result* out, hipStream_t st);
+void pgpu_small_wide_launch(const LcfIndexView& ix, const ClassView& cv, const uint8_t* ests, const pgpu_factor* exons,
+                            const pgpu_small_query* q, uint32_t n, int min_intron_length, size_t waves, pgpu_factor* out_exons,
+                            uint8_t* out_steps, pgpu_small_result* out, hipStream_t st);
