@@ -833,6 +833,105 @@ int pgpu_index_candidates(pgpu_ctx* ctx, const pgpu_index* idx, const void* reco
 double pgpu_index_candidates_kernel_ms(void);
 
 /* ------------------------------------------------------------------------------------------ */
+/* candidate lists -- every candidate factorization of a MEG that need not be one path, from   */
+/* its record: the enumeration of get_EST_factorizations (src/est-factorizations.c:160-200)    */
+/* with get_subtree_embeddings (:597-762: roots in position order, embeddings memoised per     */
+/* vertex, the maximality pruning with maximality_relation :1362-1460) and                      */
+/* get_factorizations_from_embeddings (:1292-1356).  One record = a list of candidates; each    */
+/* candidate is an exon array of the shape the chained entries above take, one query per        */
+/* candidate.  What compares candidates with each other (add_if_not_exists, FILTER 1, FILTER 3) */
+/* stays with the caller.  The parameters are pgpu_cand_params.                                 */
+/* ------------------------------------------------------------------------------------------ */
+#define PGPU_ENUM_MAX_LIST        64u   /* entries a vertex's list of embeddings may hold at any moment */
+#define PGPU_ENUM_MAX_EMBEDDINGS 512u   /* embeddings that may be created for one record                 */
+
+#define PGPU_ENUM_NONE   0u   /* the record is flagged (PGPU_MEG_UNAVAILABLE or PGPU_MEG_TOO_COMPLEX): as PGPU_CAND_NONE */
+#define PGPU_ENUM_CYCLIC 1u   /* the walk met a vertex that is on its own stack (the MEG stage never emits such a graph;
+                                 the host's recursion does not end on one) */
+#define PGPU_ENUM_RANGE  2u   /* beyond one of the two caps: detail says which; the caller enumerates on the host */
+#define PGPU_ENUM_LISTS  3u   /* answered: n_candidates candidates (a record may have none) */
+#define PGPU_ENUM_CAP_LIST       1u   /* detail of RANGE: a list held more than PGPU_ENUM_MAX_LIST entries      */
+#define PGPU_ENUM_CAP_EMBEDDINGS 2u   /* detail of RANGE: more than PGPU_ENUM_MAX_EMBEDDINGS embeddings created */
+typedef struct {
+  uint16_t kind;               /* PGPU_ENUM_* */
+  uint16_t detail;             /* RANGE: PGPU_ENUM_CAP_*; else 0 */
+  uint32_t work;               /* LISTS: one unit per vertex entered plus one per update_embedding that returned an
+                                  embedding (:626-629, :706-711); it does not depend on the order of the walk, and on a
+                                  record that is one path it is pgpu_cand_result.work.  0 for NONE, CYCLIC and RANGE.
+                                  Comparing it with a budget stays with the caller */
+  uint32_t first_candidate;    /* the record's candidates = cands[first_candidate .. first_candidate + n_candidates);
+                                  LISTS with candidates only, else 0 */
+  uint16_t n_candidates;       /* LISTS only (0 .. 512), else 0 */
+  uint16_t n_roots;            /* LISTS only: the roots the walk began at, with or without candidates */
+} pgpu_enum_result;          /* 16 bytes */
+typedef struct {
+  uint32_t first_exon;         /* the candidate = exons[first_exon .. first_exon + n_exons) */
+  uint16_t n_exons;            /* >= 1 */
+  uint16_t n_pairs;            /* pairings of the embedding */
+  uint32_t root;               /* index of the root's vertex in the record */
+  uint32_t reserved;           /* 0 */
+} pgpu_enum_candidate;       /* 16 bytes */
+
+/* Per record, with L = min_factor_len:
+ *  - A flagged record is NONE; nothing behind its 16 bytes is read.
+ *  - Roots.  The vertices are taken in record order (the reference's position-list order); one that has not been visited
+ *    yet is a root.  Entering a vertex's subtree marks it visited, whether or not its embeddings are memoised already.
+ *  - embeddings(v), computed once per vertex.  A vertex without out-edges -- any such vertex, not only the sink -- has the
+ *    single embedding [v].  Otherwise the adjacent vertices are taken in CSR order, and for every embedding e of
+ *    embeddings(adj), in list order, add = update_embedding(e, v): exactly the fold step of the candidate stage above (the
+ *    sink and source cases, the split with its two clamps, the Burset cut scan where the last of equal cuts wins).  A NULL
+ *    is skipped.  Otherwise add is compared with the list built so far, from its front: k0 is the first entry whose
+ *    maximality_relation(add, entry) is 0; the entries in front of k0 (all entries when there is no k0) whose relation is
+ *    2 are removed; add is appended only when there is no k0.
+ *  - maximality_relation(add, cmp) (:1362-1460), with "x inside y" = x.p >= y.p, x.p + x.l <= y.p + y.l and the same on t,
+ *    over the first min(|add|, |cmp|) pairings of both: |add| > |cmp|: 2 when every cmp[i] is inside add[i], else 1;
+ *    |add| < |cmp|: 0 when every add[i] is inside cmp[i], else 1; equal lengths: 0 when every add[i] is inside cmp[i],
+ *    else 2 when every cmp[i] is inside add[i], else 1.
+ *  - Candidates come root by root in root order, and within a root they are the root's embeddings in list order, each
+ *    through the exon rule of the candidate stage (a pairing x opens an exon when x.t - GEN_end - 1 > 2L).  Only roots
+ *    yield candidates.  A graph of a source and a sink without an edge has two roots and two candidates of one exon each,
+ *    which check_for_not_source_sink_factorization drops later; a record without a vertex has neither.
+ *  - The caps.  RANGE with PGPU_ENUM_CAP_LIST when a vertex's list holds more than 64 entries behind an append; with
+ *    PGPU_ENUM_CAP_EMBEDDINGS when more than 512 embeddings are created for the record, an embedding being created by a
+ *    vertex without out-edges or by an update_embedding that returned one (a copy made for the source included, and
+ *    whether or not the pruning then keeps it).  CYCLIC when an adjacent vertex is on the walk's own stack.  The walk is
+ *    the host's recursion -- depth first, an adjacent vertex's subtree before its embeddings are folded, one adjacent
+ *    vertex after the other -- and the first of the three it meets decides.  Such a record reports its kind, the
+ *    detail, and zeros.
+ *  - A source without out-edges that another vertex has an edge to (no stage emits one) is a head whose deltas leave
+ *    what int holds; as integers small_delta is below 2L, so update_embedding returns NULL for it, and that is the rule.
+ *  - Candidates of a call are compact in record order, exons in record order and then candidate order; first_candidate
+ *    and first_exon index the call's arrays. */
+
+/* Plan form: the candidate lists of the records pgpu_pairing_plan_run_meg left in HBM.  A branch beside the ladder of stages,
+ * not a rung: it asks for the records (run_meg with the same min_factor_len), changes nothing of what the plan's other
+ * stages hold, and its results stay valid until the next run or run_meg of the plan, or the run of another resident
+ * plan; after that fetch_candidate_lists is PGPU_EINVAL with a message.  run_candidates and the stages above it neither
+ * need the lists nor disturb them.  PGPU_EINVAL (with a message) as for run_candidates.  An empty plan is PGPU_OK.  A
+ * rerun gives the same bytes. */
+int pgpu_pairing_plan_run_candidate_lists(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_cand_params* params);
+/* candidates and exons of the last run_candidate_lists (either pointer may be null) */
+int pgpu_pairing_plan_candidate_list_counts(const pgpu_pairing_plan* plan, uint64_t* n_cands, uint64_t* n_exons);
+/* out: n_pat results; PGPU_ENOSPC when cands_cap or exons_cap is smaller than the counts */
+int pgpu_pairing_plan_fetch_candidate_lists(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_enum_result* out,
+                                            pgpu_enum_candidate* cands, size_t cands_cap, pgpu_factor* exons, size_t exons_cap);
+/* HIP-event time of the last run_candidate_lists (count + two scans + write); 0 without timing */
+double pgpu_pairing_plan_candidate_lists_ms(const pgpu_pairing_plan* plan);
+
+/* Index form: records, offsets, parameters and every PGPU_EINVAL as pgpu_index_candidates (the same validator).  out: n
+ * results; *n_cands, *n_exons: candidates and exons written.  PGPU_ENOSPC, with both needed counts in *n_cands and
+ * *n_exons and nothing written to out, cands or exons, when cands_cap or exons_cap is too small.  n == 0 is PGPU_OK (both
+ * counts 0).  PGPU_EINVAL (with a message) when a call's candidates or exons pass 2^32 - 1, which first_candidate and
+ * first_exon could not index: only a call of more than 131 071 records can.  idx may be built or loaded. */
+int pgpu_index_candidate_lists(pgpu_ctx* ctx, const pgpu_index* idx, const void* records, size_t records_len,
+                               const uint64_t* rec_first, size_t n, const pgpu_cand_params* params,
+                               pgpu_enum_result* out, pgpu_enum_candidate* cands, size_t cands_cap,
+                               pgpu_factor* exons, size_t exons_cap, size_t* n_cands, size_t* n_exons);
+/* HIP-event time of the kernels of the calling thread's last pgpu_index_candidate_lists (as
+ * pgpu_index_candidates_kernel_ms); 0 without timing */
+double pgpu_index_candidate_lists_kernel_ms(void);
+
+/* ------------------------------------------------------------------------------------------ */
 /* factorizations -- a candidate taken through the cleaning steps (pgpu_index_clean_chains),   */
 /* check_gap_errors (pgpu_index_gap_chains) and the refinement loop (pgpu_index_refine_chains)  */
 /* in ONE call, nothing leaving HBM in between: for an EST with exactly one candidate this is   */

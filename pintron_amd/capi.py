@@ -134,6 +134,16 @@ class CandResult(C.Structure):     # pgpu_cand_result
                 ("n_pairs", C.c_uint16)]
 
 
+class EnumResult(C.Structure):     # pgpu_enum_result
+    _fields_ = [("kind", C.c_uint16), ("detail", C.c_uint16), ("work", C.c_uint32), ("first_candidate", C.c_uint32),
+                ("n_candidates", C.c_uint16), ("n_roots", C.c_uint16)]
+
+
+class EnumCandidate(C.Structure):  # pgpu_enum_candidate
+    _fields_ = [("first_exon", C.c_uint32), ("n_exons", C.c_uint16), ("n_pairs", C.c_uint16), ("root", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class FactParams(C.Structure):     # pgpu_fact_params
     _fields_ = [("complexity_threshold", C.c_double), ("suffpref_length_on_est", C.c_int32),
                 ("suffpref_length_for_intron", C.c_int32), ("suffpref_length_on_gen", C.c_int32), ("min_intron_length", C.c_int32)]
@@ -216,6 +226,12 @@ SMALL_RESULT_DTYPE = [("status", "<i4"), ("refused", "u1"), ("verdict", "u1"), (
                       ("n_added", "<u4"), ("n_list", "<u4"), ("first_kept", "<u4"), ("n_kept", "<u4")]
 CAND_NONE, CAND_NOT_PATH, CAND_REFUSED, CAND_ONE = range(4)
 MEG_TOO_COMPLEX, MEG_UNAVAILABLE = 1, 2
+ENUM_NONE, ENUM_CYCLIC, ENUM_RANGE, ENUM_LISTS = range(4)
+ENUM_CAP_LIST, ENUM_CAP_EMBEDDINGS = 1, 2
+ENUM_MAX_LIST, ENUM_MAX_EMBEDDINGS = 64, 512
+ENUM_RESULT_DTYPE = [("kind", "<u2"), ("detail", "<u2"), ("work", "<u4"), ("first_candidate", "<u4"), ("n_candidates", "<u2"),
+                     ("n_roots", "<u2")]
+ENUM_CANDIDATE_DTYPE = [("first_exon", "<u4"), ("n_exons", "<u2"), ("n_pairs", "<u2"), ("root", "<u4"), ("reserved", "<u4")]
 CAND_PARAMS_DTYPE = [("min_factor_len", "<u4"), ("min_intron_length", "<i4")]
 CAND_RESULT_DTYPE = [("kind", "<u4"), ("work", "<u4"), ("first_exon", "<u4"), ("n_exons", "<u2"), ("n_pairs", "<u2")]
 FACT_HOST, FACT_EMPTY, FACT_DONE = range(3)
@@ -285,6 +301,8 @@ EXPORTS = [
     "pgpu_pairing_plan_meg_ms", "pgpu_host_alloc", "pgpu_host_free",
     "pgpu_pairing_plan_run_candidates", "pgpu_pairing_plan_candidate_exons", "pgpu_pairing_plan_fetch_candidates",
     "pgpu_pairing_plan_candidates_ms", "pgpu_index_candidates", "pgpu_index_candidates_kernel_ms",
+    "pgpu_pairing_plan_run_candidate_lists", "pgpu_pairing_plan_candidate_list_counts", "pgpu_pairing_plan_fetch_candidate_lists",
+    "pgpu_pairing_plan_candidate_lists_ms", "pgpu_index_candidate_lists", "pgpu_index_candidate_lists_kernel_ms",
     "pgpu_pairing_plan_run_factorizations", "pgpu_pairing_plan_factorization_exons", "pgpu_pairing_plan_fetch_factorizations",
     "pgpu_pairing_plan_factorizations_ms", "pgpu_index_factorizations", "pgpu_index_factorizations_kernel_ms",
     "pgpu_pairing_plan_create_with_originals", "pgpu_pairing_plan_run_final_factorizations", "pgpu_pairing_plan_final_exons",
@@ -391,6 +409,16 @@ def lib():
                                             C.POINTER(Factor), sz, C.POINTER(sz)]
         L.pgpu_index_candidates_kernel_ms.argtypes = []
         L.pgpu_index_candidates_kernel_ms.restype = C.c_double
+        L.pgpu_pairing_plan_run_candidate_lists.argtypes = [vp, vp, C.POINTER(CandParams)]
+        L.pgpu_pairing_plan_candidate_list_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        L.pgpu_pairing_plan_fetch_candidate_lists.argtypes = [vp, vp, C.POINTER(EnumResult), C.POINTER(EnumCandidate), sz,
+                                                              C.POINTER(Factor), sz]
+        L.pgpu_pairing_plan_candidate_lists_ms.argtypes = [vp]
+        L.pgpu_pairing_plan_candidate_lists_ms.restype = C.c_double
+        L.pgpu_index_candidate_lists.argtypes = [vp, vp, vp, sz, C.POINTER(u64), sz, C.POINTER(CandParams), C.POINTER(EnumResult),
+                                                 C.POINTER(EnumCandidate), sz, C.POINTER(Factor), sz, C.POINTER(sz), C.POINTER(sz)]
+        L.pgpu_index_candidate_lists_kernel_ms.argtypes = []
+        L.pgpu_index_candidate_lists_kernel_ms.restype = C.c_double
         L.pgpu_pairing_plan_run_factorizations.argtypes = [vp, vp, C.POINTER(FactParams)]
         L.pgpu_pairing_plan_factorization_exons.argtypes = [vp]
         L.pgpu_pairing_plan_factorization_exons.restype = u64
@@ -802,6 +830,38 @@ class Index:
     def candidates_kernel_ms(self):
         return self.ctx.L.pgpu_index_candidates_kernel_ms()
 
+    def candidate_lists_raw(self, records: bytes, rec_first, n: int, min_factor_len, min_intron_length, cands_cap: int, exons_cap: int):
+        """One pgpu_index_candidate_lists call as it is (the arguments of candidates_raw).  Returns (rc, results as a numpy array
+        of ENUM_RESULT_DTYPE, candidates (cands_cap entries of ENUM_CANDIDATE_DTYPE), exons (exons_cap entries), n_cands,
+        n_exons)."""
+        import numpy as np
+        res = np.zeros(n, dtype=np.dtype(ENUM_RESULT_DTYPE))
+        cands = np.zeros(cands_cap, dtype=np.dtype(ENUM_CANDIDATE_DTYPE))
+        exons = np.zeros(exons_cap, dtype=np.dtype(FACTOR_DTYPE))
+        prm = CandParams(min_factor_len, min_intron_length)
+        nc, ne = C.c_size_t(0), C.c_size_t(0)
+        rc = self.ctx.L.pgpu_index_candidate_lists(
+            self.ctx.h, self.h, records, len(records), rec_first.ctypes.data_as(C.POINTER(C.c_uint64)), n, C.byref(prm),
+            res.ctypes.data_as(C.POINTER(EnumResult)), cands.ctypes.data_as(C.POINTER(EnumCandidate)), cands_cap,
+            exons.ctypes.data_as(C.POINTER(Factor)), exons_cap, C.byref(nc), C.byref(ne))
+        return rc, res, cands, exons, nc.value, ne.value
+
+    def candidate_lists(self, records, min_factor_len=15, min_intron_length=40):
+        """Every candidate factorization of every MEG record of the list `records`: (results as a numpy array of
+        ENUM_RESULT_DTYPE, candidates as one of ENUM_CANDIDATE_DTYPE, exons as one of FACTOR_DTYPE)."""
+        import numpy as np
+        first = np.zeros(len(records) + 1, dtype=np.uint64)
+        np.cumsum([len(r) for r in records], out=first[1:])
+        blob = b"".join(records)
+        rc, res, cands, exons, nc, ne = self.candidate_lists_raw(blob, first, len(records), min_factor_len, min_intron_length, 0, 0)
+        if rc == PGPU_ENOSPC:
+            rc, res, cands, exons, nc, ne = self.candidate_lists_raw(blob, first, len(records), min_factor_len, min_intron_length, nc, ne)
+        self.ctx.check(rc)
+        return res, cands[:nc], exons[:ne]
+
+    def candidate_lists_kernel_ms(self):
+        return self.ctx.L.pgpu_index_candidate_lists_kernel_ms()
+
     def factorizations_raw(self, ests: bytes, exons, queries, n: int, params, cap: int):
         """One pgpu_index_factorizations call as it is: `exons` a numpy array of FACTOR_DTYPE, `queries` one of
         FACT_QUERY_DTYPE, `params` a FactParams.  Returns (rc, results as a numpy array of FACT_RESULT_DTYPE, exons and step
@@ -1133,6 +1193,34 @@ class PairingPlan:
 
     def candidates_ms(self):
         return self.ctx.L.pgpu_pairing_plan_candidates_ms(self.h)
+
+    def run_candidate_lists(self, min_factor_len=15, min_intron_length=40):
+        """every candidate of the records of the last run_meg, which stay in HBM; a branch beside the stages: it changes
+        nothing of what they hold.  Returns (candidates, exons)."""
+        prm = CandParams(min_factor_len, min_intron_length)
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_run_candidate_lists(self.ctx.h, self.h, C.byref(prm)))
+        return self.candidate_list_counts()
+
+    def candidate_list_counts(self):
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.L.pgpu_pairing_plan_candidate_list_counts(self.h, C.byref(nc), C.byref(ne))
+        return nc.value, ne.value
+
+    def fetch_candidate_lists(self):
+        """(results as a numpy array of ENUM_RESULT_DTYPE, one per pattern; candidates as one of ENUM_CANDIDATE_DTYPE; exons
+        as one of FACTOR_DTYPE)"""
+        import numpy as np
+        nc, ne = self.candidate_list_counts()
+        res = np.zeros(self.n_pat, dtype=np.dtype(ENUM_RESULT_DTYPE))
+        cands = np.zeros(nc, dtype=np.dtype(ENUM_CANDIDATE_DTYPE))
+        exons = np.zeros(ne, dtype=np.dtype(FACTOR_DTYPE))
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_fetch_candidate_lists(
+            self.ctx.h, self.h, res.ctypes.data_as(C.POINTER(EnumResult)), cands.ctypes.data_as(C.POINTER(EnumCandidate)), nc,
+            exons.ctypes.data_as(C.POINTER(Factor)), ne))
+        return res, cands, exons
+
+    def candidate_lists_ms(self):
+        return self.ctx.L.pgpu_pairing_plan_candidate_lists_ms(self.h)
 
     def run_factorizations(self, complexity_threshold=20.0, suffpref_length_on_est=30, suffpref_length_for_intron=70,
                            suffpref_length_on_gen=30, min_intron_length=40):

@@ -95,6 +95,7 @@ enum PlanSlot : int {
   SLOT_UNITS,
   SLOT_TEXTS, SLOT_TEXT_BLOBS,
   SLOT_SIDES, SLOT_SIDE_BLOBS,
+  SLOT_ENUM, SLOT_ENUM_OUT,
   PLAN_SLOTS
 };
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool);
@@ -131,6 +132,14 @@ void pgpu_cand_launch_count(const uint8_t* recs, const unsigned long long* rec_f
 void pgpu_cand_launch_write(const uint8_t* recs, const unsigned long long* rec_first, uint32_t n, const uint8_t* T, uint32_t tlen,
                             const pgpu_cand_params* prm, pgpu_cand_result* res, const unsigned long long* first_exon,
                             pgpu_factor* exons, hipStream_t st);
+// pgpu_enum.hip: every candidate of every record of a batch of MEG records, in two launches around two exclusive scans (of
+// cnt_c and cnt_e, n + 1 entries each, the last one 0): the count pass fills res and the counts, the write pass
+// first_candidate, the candidate table and the exons.  The error is that of asking the device for its grid.
+hipError_t pgpu_enum_launch_count(const uint8_t* recs, const unsigned long long* rec_first, uint32_t n, const uint8_t* T, uint32_t tlen,
+                                  const pgpu_cand_params* prm, pgpu_enum_result* res, uint32_t* cnt_c, uint32_t* cnt_e, hipStream_t st);
+hipError_t pgpu_enum_launch_write(const uint8_t* recs, const unsigned long long* rec_first, uint32_t n, const uint8_t* T, uint32_t tlen,
+                                  const pgpu_cand_params* prm, pgpu_enum_result* res, const unsigned long long* first_c,
+                                  const unsigned long long* first_e, pgpu_enum_candidate* cands, pgpu_factor* exons, hipStream_t st);
 // pgpu_fact.hip: the candidates of n ESTs through clean, gaps and refine, all on the device.  The caller fills everything but
 // the two results; `block` holds fact_layout(n, n_exons_total, pgpu_scan_tmp_bytes(n + 1)).total bytes (pgpu_fact.h), where
 // the outcomes (res), the compact exons and their step bytes are found afterwards.  The candidates are either queries

@@ -20,6 +20,7 @@
 
 #include "pgpu_index.h"
 #include "pgpu_stage_drive.h"
+#include "pgpu_enum.h"
 #include "pgpu_fact.h"
 #include "pgpu_final.h"
 #include "pgpu_unit.h"
@@ -371,12 +372,16 @@ void pair_emit_kernel(const unsigned long long* __restrict__ pat_off,
 // compare one), and raises the plan to k when it succeeds.  A fetch of stage k asks for stage k.  A plan without
 // patterns has nothing to compute: its runs succeed without their predecessor (run_factorizations and the stages above
 // it still ask for theirs), and fetch and fetch_meg answer whatever ran.
+// The candidate lists (run_candidate_lists, pgpu_enum.hip) are a branch beside this ladder, not a rung: the run asks for
+// RECORDS made with the same min_factor_len and never changes `stage`; its results live in pool slots of their own
+// (SLOT_ENUM, SLOT_ENUM_OUT) under a flag of their own (lists_valid), which run and run_meg clear and which the run of
+// another resident plan overrules (overwritten); run_candidates and the rungs above it neither need nor disturb them.
 enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS, UNITS, TEXTS, SIDES };
 
 // the plan's events (made only when the context times its calls): seven around the six pairing stages, a pair each for
 // the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job, the pair of pgpu_unit_job, the
-// three of pgpu_text_job, the three of pgpu_side_job
-enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, EV_TEXTS = 27, EV_SIDES = 30, N_EVENTS = 33 };
+// three of pgpu_text_job, the three of pgpu_side_job, the pair of the candidate lists
+enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, EV_TEXTS = 27, EV_SIDES = 30, EV_LISTS = 33, N_EVENTS = 35 };
 
 struct pgpu_pairing_plan {
   pgpu_ctx* owner = nullptr;
@@ -456,6 +461,13 @@ struct pgpu_pairing_plan {
   unsigned long long side_total[3] = {0, 0, 0};
   bool side_timed = false;                             // the write pass's event is still to be waited for
   float side_ms = 0.f, side_write_ms = 0.f;
+  // candidate lists (pgpu_enum.hip) over the records of the last run_meg, beside the ladder: the block of enum_layout
+  // (pgpu_enum.h; results, counts, offsets) and the one of enum_out_layout (candidate table, exons), sized after the scans
+  uint8_t *d_lists = nullptr, *d_lists_out = nullptr;
+  size_t lists_cap = 0, lists_out_cap = 0;
+  unsigned long long lists_cands = 0, lists_exons = 0;
+  bool lists_valid = false;
+  float lists_ms = 0.f;
 };
 
 static void lower(pgpu_pairing_plan* p, Stage s) { if (p->stage > s) p->stage = s; }
@@ -562,7 +574,7 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_meg_scratch); hipFree(p->d_meg_info); hipFree(p->d_meg_bytes); hipFree(p->d_meg_off); hipFree(p->d_meg_out);
     hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
     hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final); hipFree(p->d_unit); hipFree(p->d_text); hipFree(p->d_text_blobs);
-    hipFree(p->d_side); hipFree(p->d_side_blobs);
+    hipFree(p->d_side); hipFree(p->d_side_blobs); hipFree(p->d_lists); hipFree(p->d_lists_out);
     if (p->d_orig_off != p->d_pat_off) hipFree(p->d_orig_off);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
@@ -659,6 +671,7 @@ extern "C" int pgpu_pairing_plan_run(pgpu_ctx* ctx, pgpu_pairing_plan* p, const 
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   p->n_cand = p->n_out = 0;
   lower(p, NOTHING);
+  p->lists_valid = false;
   p->last_L = params->min_factor_len;
   if (p->n_pat == 0) return reached(p, PAIRINGS);
   if (p->resident) {
@@ -724,6 +737,7 @@ extern "C" int pgpu_pairing_plan_run_meg(pgpu_ctx* ctx, pgpu_pairing_plan* p, co
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   p->meg_total = 0; p->meg_ms = 0.f;
   lower(p, PAIRINGS);
+  p->lists_valid = false;
   if (p->n_pat == 0) return reached(p, RECORDS);
   if (p->stage < PAIRINGS || p->last_L != prm->min_factor_len)
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_meg needs the pairings of pgpu_pairing_plan_run with the same min_factor_len");
@@ -820,6 +834,82 @@ extern "C" int pgpu_pairing_plan_fetch_candidates(pgpu_ctx* ctx, pgpu_pairing_pl
   if (p->n_pat == 0) return PGPU_OK;
   PLAN_TRY(hipMemcpyAsync(out, p->d_cand_res, p->n_pat * sizeof(pgpu_cand_result), hipMemcpyDeviceToHost, st));
   if (p->cand_total) PLAN_TRY(hipMemcpyAsync(exons, p->d_cand_exons, (size_t)p->cand_total * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
+  PLAN_TRY(pgpu_ctx_wait(ctx));
+  return PGPU_OK;
+}
+
+// ---- every candidate of every record that pgpu_pairing_plan_run_meg left in HBM (pgpu_enum.hip); beside the ladder ----
+extern "C" int pgpu_pairing_plan_run_candidate_lists(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_cand_params* prm) {
+  if (!ctx || !p || !prm) return PGPU_EINVAL;
+  p->lists_cands = p->lists_exons = 0; p->lists_ms = 0.f;
+  p->lists_valid = false;                              // its own results are gone, even when the call is then refused
+  if (prm->min_factor_len == 0 || prm->min_factor_len > (1u << 24))
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad candidate parameters (min_factor_len 0 or above 2^24)");
+  if (p->n_pat == 0) { p->lists_valid = true; return PGPU_OK; }
+  if (p->stage < RECORDS || p->meg_L != prm->min_factor_len)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_candidate_lists needs the records of pgpu_pairing_plan_run_meg with the same min_factor_len");
+  if (const int rc = still_owns(ctx, p, "records")) return rc;
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  const uint32_t np = (uint32_t)p->n_pat;
+  const PairIndexView& ix = p->ix;
+  const ProfRange range("candidate lists");
+  const EnumLayout E = enum_layout(0, np, 0);
+  PLAN_NEED(p->d_lists = stage_block(p, p->d_lists, &p->lists_cap, E.total, SLOT_ENUM));
+  PLAN_TRY(plan_events(p, EV_LISTS, 2));
+  pgpu_enum_result* const d_res = (pgpu_enum_result*)(p->d_lists + E.res);
+  uint32_t* const d_cnt_c = (uint32_t*)(p->d_lists + E.cnt_c);
+  uint32_t* const d_cnt_e = (uint32_t*)(p->d_lists + E.cnt_e);
+  unsigned long long* const d_off_c = (unsigned long long*)(p->d_lists + E.off_c);
+  unsigned long long* const d_off_e = (unsigned long long*)(p->d_lists + E.off_e);
+  PLAN_TRY(drive_record(p->ev, EV_LISTS, st));
+  PLAN_TRY(pgpu_enum_launch_count(p->d_meg_out, p->d_meg_off, np, ix.T, ix.n, prm, d_res, d_cnt_c, d_cnt_e, st));
+  unsigned long long total_c = 0, total_e = 0;
+  PLAN_TRY(drive_scan(d_cnt_c, d_off_c, np, p->d_tmp, st));
+  PLAN_TRY(hipMemcpyAsync(&total_c, d_off_c + np, sizeof total_c, hipMemcpyDeviceToHost, st));
+  PLAN_TRY(scan_total(ctx, p, d_cnt_e, d_off_e, np, nullptr, &total_e));
+  if (!enum_totals_fit(total_c, total_e))
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^32 - 1 candidates or exons in one plan");
+  const EnumOutLayout O = enum_out_layout((size_t)total_c, (size_t)total_e);
+  PLAN_NEED(p->d_lists_out = stage_block(p, p->d_lists_out, &p->lists_out_cap, O.total, SLOT_ENUM_OUT));
+  PLAN_TRY(pgpu_enum_launch_write(p->d_meg_out, p->d_meg_off, np, ix.T, ix.n, prm, d_res, d_off_c, d_off_e,
+                                  (pgpu_enum_candidate*)(p->d_lists_out + O.cands), (pgpu_factor*)(p->d_lists_out + O.exons), st));
+  PLAN_TRY(drive_record(p->ev, EV_LISTS + 1, st));
+  PLAN_TRY(pgpu_ctx_wait(ctx));
+  PLAN_TRY(hipGetLastError());
+  elapsed_pairs(p, EV_LISTS, 1, &p->lists_ms);
+  p->lists_cands = total_c; p->lists_exons = total_e;
+  p->lists_valid = true;
+  return PGPU_OK;
+}
+
+extern "C" int pgpu_pairing_plan_candidate_list_counts(const pgpu_pairing_plan* p, uint64_t* n_cands, uint64_t* n_exons) {
+  if (!p) return PGPU_EINVAL;
+  if (n_cands) *n_cands = p->lists_cands;
+  if (n_exons) *n_exons = p->lists_exons;
+  return PGPU_OK;
+}
+extern "C" double pgpu_pairing_plan_candidate_lists_ms(const pgpu_pairing_plan* p) { return p ? p->lists_ms : 0.0; }
+
+extern "C" int pgpu_pairing_plan_fetch_candidate_lists(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_enum_result* out,
+                                                       pgpu_enum_candidate* cands, size_t cands_cap, pgpu_factor* exons,
+                                                       size_t exons_cap) {
+  if (!ctx || !p || (p->n_pat && !out) || (cands_cap && !cands) || (exons_cap && !exons)) return PGPU_EINVAL;
+  if (const int rc = still_owns(ctx, p, "candidate lists")) return rc;
+  if (!p->lists_valid)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_candidate_lists needs pgpu_pairing_plan_run_candidate_lists behind the last run and run_meg");
+  if (cands_cap < p->lists_cands) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "candidate buffer too small");
+  if (exons_cap < p->lists_exons) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_pat == 0) return PGPU_OK;
+  const EnumLayout E = enum_layout(0, p->n_pat, 0);
+  const EnumOutLayout O = enum_out_layout((size_t)p->lists_cands, (size_t)p->lists_exons);
+  PLAN_TRY(hipMemcpyAsync(out, p->d_lists + E.res, p->n_pat * sizeof(pgpu_enum_result), hipMemcpyDeviceToHost, st));
+  if (p->lists_cands)
+    PLAN_TRY(hipMemcpyAsync(cands, p->d_lists_out + O.cands, (size_t)p->lists_cands * sizeof(pgpu_enum_candidate), hipMemcpyDeviceToHost, st));
+  if (p->lists_exons)
+    PLAN_TRY(hipMemcpyAsync(exons, p->d_lists_out + O.exons, (size_t)p->lists_exons * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
   PLAN_TRY(pgpu_ctx_wait(ctx));
   return PGPU_OK;
 }

@@ -1012,6 +1012,59 @@ unsigned ef_chain_candidate(const void* rec, const ef_config* cfg, const char* G
   return 3;
 }
 
+/* Every candidate of one MEG record as pgpu_pairing_plan_run_candidate_lists / pgpu_index_candidate_lists define them
+ * (include/pintron_gpu.h): the lists made for the record (ef_meg_from_record), the root loop of ef_get_est_factorizations
+ * with subtree_embeddings, and factorizations_from_embeddings, flattened.  cand_first[c] .. cand_first[c + 1] delimits the
+ * exons of candidate c in out_exons, cand_root[c] is its root's vertex and cand_pairs[c] its embedding's length; at most
+ * cand_cap candidates (cand_first holds cand_cap + 1 entries) and exon_cap exons are written, *n_cands and *n_exons are
+ * the numbers there are.  Returns 0 when the record is flagged (nothing else is set), else 3.  No budget and no cap: *work
+ * is what the enumeration charged, and a cyclic graph does not return.  est-fact does not call this (cold). */
+__attribute__((cold)) unsigned ef_chain_candidates(const void* rec, const ef_config* cfg, const char* GEN, ef_factor* out_exons,
+                                                   size_t exon_cap, unsigned* cand_first, unsigned* cand_root, unsigned* cand_pairs,
+                                                   size_t cand_cap, unsigned* n_cands, unsigned* n_exons, unsigned* n_roots,
+                                                   unsigned* work) {
+  *n_cands = 0; *n_exons = 0; *n_roots = 0; *work = 0;
+  if (((const uint32_t*)rec)[2] & 3u) return 0;
+  ef_meg* V = ef_meg_from_record(rec, 0);
+  ef_work wk = { 0, ~0ull };
+  const ef_pairing* base = NULL;                        /* the vertices lie in one array in record order: the first is [0] */
+  EF_MEG_FOR_POS(V, i, 0, V->n_act) {
+    ef_iter it = efl_begin(V->v[i]);
+    while (efi_has_next(&it)) {
+      ef_pairing* root = (ef_pairing*)efi_next(&it);
+      if (!base) base = root;
+      if (root->visited) continue;
+      ++*n_roots;
+      ef_list* embs = subtree_embeddings(root, cfg, GEN, &wk);
+      ef_list* cands = factorizations_from_embeddings(embs, cfg);
+      ef_iter ei = efl_begin(embs);
+      ef_iter ci = efl_begin(cands);
+      while (efi_has_next(&ci)) {
+        ef_list* fact = (ef_list*)efi_next(&ci);
+        const emb* em = (const emb*)efi_next(&ei);
+        if (*n_cands < cand_cap) { cand_first[*n_cands] = *n_exons; cand_root[*n_cands] = (unsigned)(root - base); cand_pairs[*n_cands] = em->n; }
+        ef_iter xi = efl_begin(fact);
+        while (efi_has_next(&xi)) {
+          const ef_factor* x = (const ef_factor*)efi_next(&xi);
+          if (*n_exons < exon_cap) out_exons[*n_exons] = *x;
+          ++*n_exons;
+        }
+        ++*n_cands;
+        if (*n_cands <= cand_cap) cand_first[*n_cands] = *n_exons;
+        ef_factorization_free(fact);
+      }
+      efl_free(cands, NULL);
+    }
+  }
+  EF_MEG_FOR_POS(V, i, 0, V->n_act) {
+    ef_iter it = efl_begin(V->v[i]);
+    while (efi_has_next(&it)) { ef_pairing* p = (ef_pairing*)efi_next(&it); if (p->emb_memo) { efl_free(p->emb_memo, embedding_free); p->emb_memo = NULL; } }
+  }
+  ef_meg_free(V);
+  *work = (unsigned)wk.used;
+  return 3;
+}
+
 /* What get_EST_factorizations does to the cleaned candidates of one EST before correct_tail: FILTER 1, FILTER 3, FILTER 4
  * (check_gap_errors), max_number_of_factorizations and the intron refinement loop with its first-exon rule (:278-490).
  * Returns the list (it may be a new one).  Shared by ef_get_est_factorizations and ef_chain_factorization. */

@@ -415,6 +415,13 @@ typedef struct { int EST_start, EST_end, GEN_start, GEN_end; } ef_factor;   /* 0
  * 3 one candidate with its exons, the embedding's length and the work units charged (ef_fact.c) */
 unsigned ef_chain_candidate(const void* rec, const ef_config* cfg, const char* GEN, ef_factor* out_exons, size_t cap,
                             unsigned* n_exons, unsigned* n_pairs, unsigned* work);
+/* every candidate of one MEG record, whatever its shape: 0 flagged, else 3 with the candidates' exons (candidate c =
+ * out_exons[cand_first[c] .. cand_first[c + 1])), roots and embedding lengths, the number of roots and the work units
+ * charged (ef_fact.c).  What pgpu_pairing_plan_run_candidate_lists answers on the device, without its caps; est-fact does
+ * not call it */
+unsigned ef_chain_candidates(const void* rec, const ef_config* cfg, const char* GEN, ef_factor* out_exons, size_t exon_cap,
+                             unsigned* cand_first, unsigned* cand_root, unsigned* cand_pairs, size_t cand_cap, unsigned* n_cands,
+                             unsigned* n_exons, unsigned* n_roots, unsigned* work);
 /* one MEG record and one EST (working sequences, NUL-terminated) through everything ef_get_est_factorizations does for a
  * graph that is one path, up to, not including, correct_tail: 0 not one path (or flagged), 1 no factorization, 2 the exons
  * (ef_fact.c).  What pgpu_pairing_plan_run_factorizations answers on the device; est-fact does not call it */
