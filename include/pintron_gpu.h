@@ -1021,6 +1021,151 @@ int pgpu_index_factorizations(pgpu_ctx* ctx, const pgpu_index* idx, const char* 
 double pgpu_index_factorizations_kernel_ms(void);
 
 /* ------------------------------------------------------------------------------------------ */
+/* factorization lists -- every candidate of one EST (pgpu_index_candidate_lists' output as it  */
+/* is) to the list of factorizations get_EST_factorizations (src/est-factorizations.c:203-490)  */
+/* holds just before correct_composition_tail: the cleaning steps per candidate,               */
+/* add_if_not_exists (:2041-2109) folded over the survivors, FILTER 1 (:278-331), FILTER 3      */
+/* (:376-414), check_gap_errors per entry (FILTER 4), max_number_of_factorizations (:438-442)   */
+/* and the refinement loop per entry, in ONE call, nothing leaving HBM in between.  The three   */
+/* stage kernels are the ones of the chained entries, one query per candidate; what compares    */
+/* candidates with each other is one wave per EST.                                              */
+/* ------------------------------------------------------------------------------------------ */
+#define PGPU_FLIST_MAX_CANDIDATES 64u   /* candidates of one EST (one lane per list entry); beyond: HOST at stage 0 */
+#define PGPU_FLIST_CAP_CANDIDATES  4u   /* detail of HOST at stage 0 for that cap (0 .. 2 are enumeration kinds) */
+typedef struct {
+  double  complexity_threshold;       /* clean: config->complexity_threshold */
+  int32_t suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen;   /* refine: each in [0, 2^24] */
+  int32_t min_intron_length;          /* refine: config->min_intron_length; only compared: any value */
+  double  max_coverage_diff;          /* FILTER 1: config->max_coverage_diff, in [0, 1] */
+  int32_t max_site_difference;        /* add_if_not_exists: (int) config->max_site_difference, in [0, 2^24] */
+  int32_t max_gaplength_diff;         /* FILTER 3: config->max_gapLength_diff, >= -1; -1 switches the filter off */
+  int32_t max_number_of_factorizations;   /* :438-442, in [0, 2^24]; 0 switches the rule off.  A negative value is
+                                             PGPU_EINVAL: what the reference does with one stays with the caller */
+  uint32_t reserved;                  /* 0 */
+} pgpu_flist_params;         /* 48 bytes: 0, 8, 12, 16, 20, 24, 32, 36, 40, 44; no padding */
+typedef struct {
+  uint64_t est_off; uint32_t est_len; /* EST_seq = ests + est_off, est_len bytes, 1 .. 2^31 - 1: est_len stands both for
+                                         pext->size - 2 and for strlen(EST) */
+  uint32_t first_candidate, n_candidates;   /* the EST's candidates = cands[first_candidate .. + n_candidates), in the
+                                               enumeration stage's order (root by root, within a root in list order) */
+  uint32_t reserved;                  /* 0 */
+} pgpu_flist_query;          /* 24 bytes: 0, 8, 12, 16, 20; no padding */
+typedef struct {
+  uint8_t  outcome;          /* PGPU_FACT_HOST, PGPU_FACT_EMPTY or PGPU_FACT_DONE */
+  uint8_t  stage;            /* where the outcome fell: 0 candidates, 1 clean, 2 select, 3 gaps, 4 refine */
+  uint16_t detail;           /* HOST at stage 0: PGPU_FLIST_CAP_CANDIDATES (plan form also: the enumeration kind NONE, CYCLIC,
+                                RANGE); at stages 1, 3, 4: 1 a cap (that entry's PGPU_ERANGE), 2 an input that entry's validator
+                                refuses.  EMPTY: 0, but at stage 3: 1 every entry dropped by check_gap_errors, 2 more entries
+                                left than max_number_of_factorizations.  DONE: 0 */
+  uint32_t first_fact;       /* DONE only, else 0: facts[first_fact .. first_fact + n_facts), in flist order */
+  uint16_t n_facts;          /* DONE only (>= 1), else 0 */
+  uint16_t n_cleaned;        /* the list's length after clean, */
+  uint16_t n_listed;         /* after add_if_not_exists, */
+  uint16_t n_filtered;       /* and after FILTER 3: each whenever that point was reached, else 0 */
+} pgpu_flist_result;         /* 16 bytes: 0, 1, 2, 4, 8, 10, 12, 14 */
+#define PGPU_FLIST_DROPPED_FIRST 1u   /* flags bit 0: dropped_first of pgpu_chain_result (the exon is not among the n_exons) */
+#define PGPU_FLIST_HEAD_WIDENED  2u   /* bit 1: an equal candidate (res == -2) gave the head its EST_start and GEN_start */
+#define PGPU_FLIST_TAIL_WIDENED  4u   /* bit 2: ... the tail its EST_end and GEN_end */
+typedef struct {
+  uint32_t first_exon;       /* exons[first_exon .. first_exon + n_exons), steps likewise (as pgpu_index_factorizations') */
+  uint16_t n_exons;          /* >= 1 */
+  uint16_t n_merged;         /* exons check_gap_errors merged into the one before them */
+  uint32_t candidate;        /* index, in the call's table, of the candidate the factorization began as */
+  uint16_t total_edit;       /* tot_out_edit_distance of check_gap_errors (<= PGPU_GAPS_MAX_ERRORS) */
+  uint16_t flags;            /* PGPU_FLIST_* */
+} pgpu_flist_fact;           /* 16 bytes: 0, 4, 6, 8, 12, 14 */
+
+/* Per EST, with its candidates c0 .. c(m-1).  clean_candidates is called per root on one growing flist, so the rule is a
+ * flat fold in candidate order.
+ *  0. m == 0: EMPTY at stage 0.  m > PGPU_FLIST_MAX_CANDIDATES: HOST at stage 0, detail PGPU_FLIST_CAP_CANDIDATES.
+ *  1. Every candidate goes through pgpu_index_clean_chains' steps on a query of its own.  A candidate that gets
+ *     PGPU_ERANGE (detail 1), or is a query that entry's validator refuses (detail 2: a coordinate outside its string, an
+ *     end exon of a list that passes step 1 beginning in front of or ending behind its string), makes the EST HOST at stage
+ *     1; the lowest such candidate index decides the detail.  Verdicts 1 .. 7 drop that candidate only.  None left: EMPTY.
+ *  2. add_if_not_exists over the survivors (their kept runs [first_kept, first_kept + n_kept) of clean's out_exons), in
+ *     candidate order.  to_add is compared with every list entry from the front; res is
+ *       - both of one exon (:2053-2066): -2 when GEN_start and GEN_end are equal, else -1 when to_add lies inside the entry
+ *         on the genomic sequence (>=, <=), else 1 when the entry lies inside to_add, else 0;
+ *       - else relaxed_list_contained(to_add, entry, relaxed_factor_compare, max_site_difference) (src/list.c:320-483):
+ *         equal lengths: -2 when every pair compares 0 under cfr_type -2 for the first, -1 for the last and 0 between (two
+ *         lists of one exon never get here; a list of one exon against a longer one is 0); unequal lengths: the shorter
+ *         list's first exon is looked for along the longer one (cfr_type -2 at the longer one's first exon, 2 behind it),
+ *         then both advance together under cfr_type 0, and for the shorter list's last exon 1, or -1 when it meets the
+ *         longer list's last; a mismatch is 0; when the shorter list is used up exactly: 1 when to_add is the longer one,
+ *         -1 when it is the shorter one.  The loop counts a step even when it ends on a list's end, so a shorter list whose
+ *         exons run out of partners is 0.
+ *       - relaxed_factor_compare(p1, p2, cfr_type, allowed, l1) (src/est-factorizations.c:1159-1259), p1 always of the
+ *         longer list l1 (of to_add for equal lengths): 1 when the two exons do not overlap on the genomic sequence
+ *         (strictly apart); cfr_type 0: 0 when both genomic ends differ by at most `allowed`; |cfr_type| 2: the ends agree;
+ *         for +2, p1.GEN_start - p2.GEN_start > 20 (max_unconf) is 1, and when it is > 0 with tot = the genomic lengths of
+ *         l1's exons in front of the one that begins where p1 does, |p1.GEN_start - p2.GEN_start - tot| < 10 is 1; else 0;
+ *         |cfr_type| 1: the starts agree; for +1 the same with p2.GEN_end - p1.GEN_end, tot summed from l1's back, and the
+ *         constant 20; whatever matches no branch is 1.
+ *     The first entry with res < 0 stops the walk and to_add is not added; when that res is -2 the entry's head takes
+ *     EST_start and GEN_start of to_add's head if to_add's EST_start is smaller, and its tail EST_end and GEN_end of
+ *     to_add's tail if that EST_end is larger (in place: later compares see the widened entry).  Entries in front of the
+ *     stop with res == 1 are removed -- all such entries when nothing stops the walk, and then to_add is appended.  The
+ *     list's order is the order of appends, which is candidate order.
+ *     FILTER 1: cov = (double)(est_len - (head.EST_start + (est_len - tail.EST_end - 1))) / (double) est_len, int and FP64
+ *     as :1262-1273; max_cov over the list from 0.0; an entry goes when max_cov - cov > max_coverage_diff, else when
+ *     (max_cov - cov) * (double)(int) est_len > 100.  An entry of one exon with EST_start outside [0, est_len) goes first
+ *     (:290-296; clean's verdict 1 lets none arrive).  No product is contracted into an FMA.
+ *     FILTER 3, on what FILTER 1 left: g = the sum of EST_start - previous EST_end - 1 over the entry (0 for one exon);
+ *     min_gl is folded over the list from -1 by `min_gl == -1 || min_gl > g` -- a minimum that has become -1 (exons that
+ *     share an EST byte) is replaced by the next entry's g whatever that is, as :389-392 do; an entry goes when
+ *     max_gaplength_diff != -1 and g - min_gl > max_gaplength_diff.  Neither filter can empty the list.
+ *  3. Every entry left goes through pgpu_index_gap_chains' steps with its merged ends.  An entry that entry's validator
+ *     refuses (detail 2) or PGPU_ERANGE (detail 1): HOST at stage 3, the lowest candidate index deciding.  Verdict 1 drops
+ *     the entry.  None left: EMPTY, detail 1.  Then, when max_number_of_factorizations != 0 and more entries are left
+ *     than that: EMPTY, detail 2.
+ *  4. Every entry left, less the exons gaps merged, goes through pgpu_index_refine_chains' steps with the call's four
+ *     settings.  Two adjacent exons not strictly in order (detail 2) or PGPU_ERANGE (detail 1): HOST at stage 4, the lowest
+ *     candidate index deciding.  Otherwise DONE: the factorizations in flist order, each with the first-exon rule
+ *     (:476-485) applied.
+ *  - An outcome never depends on another EST of the call; a candidate a filter or a verdict removed runs the later stages'
+ *    trivial queries on a placeholder exon of its own and never reaches a later cap.  The work budget stays with the caller.
+ *  - facts, exons and steps of a call are compact: EST order, then list order.  The step bytes are as in
+ *    pgpu_index_factorizations. */
+
+/* Index form.  cands: n_cands_total entries, as pgpu_index_candidate_lists writes them (n_pairs and root are not looked at);
+ * exons: n_exons_total entries.  out: n results; facts: facts_cap entries; out_exons, out_steps: exons_cap entries;
+ * *n_facts, *n_exons: what was written.  One upload, one download.
+ *  - PGPU_EINVAL for the whole call only for structure: a null pointer (no message); est_off + est_len > ests_len;
+ *    est_len == 0 or > 2^31 - 1; a reserved word != 0 (query, named candidate, parameters); first_candidate + n_candidates
+ *    > n_cands_total; a named candidate with n_exons == 0 or first_exon + n_exons > n_exons_total; two queries sharing a
+ *    candidate; two candidates sharing an exon; a parameter outside the range stated above; more than 2^31 - 1 queries,
+ *    candidates or exons.  A candidate no query names is not looked at.  Whatever concerns the VALUES of the exons is
+ *    HOST for that EST.
+ *  - PGPU_ENOSPC, with both needed counts in *n_facts and *n_exons and nothing written to out, facts, out_exons or
+ *    out_steps, when facts_cap or exons_cap is too small.
+ *  - n == 0 is PGPU_OK (both counts 0).  idx may be built or loaded. */
+int pgpu_index_factorization_lists(pgpu_ctx* ctx, const pgpu_index* idx, const char* ests, size_t ests_len,
+                                   const pgpu_enum_candidate* cands, size_t n_cands_total, const pgpu_factor* exons,
+                                   size_t n_exons_total, const pgpu_flist_query* q, size_t n, const pgpu_flist_params* params,
+                                   pgpu_flist_result* out, pgpu_flist_fact* facts, size_t facts_cap, pgpu_factor* out_exons,
+                                   uint8_t* out_steps, size_t exons_cap, size_t* n_facts, size_t* n_exons);
+/* HIP-event time of the whole device part of the calling thread's last pgpu_index_factorization_lists on a context with
+ * timing on (as pgpu_index_find_kernel_ms); 0 without timing */
+double pgpu_index_factorization_lists_kernel_ms(void);
+
+/* Plan form: the candidate lists of the last pgpu_pairing_plan_run_candidate_lists, where they lie; the ESTs are the plan's
+ * patterns.  A second branch beside the ladder, as run_candidate_lists is: it needs valid candidate lists, changes nothing
+ * of what the plan's other stages hold, and its results stay valid until the next run, run_meg or run_candidate_lists of
+ * the plan, or the run of another resident plan; after that fetch_factorization_lists is PGPU_EINVAL with a message.  A
+ * record whose enumeration kind is NONE, CYCLIC or RANGE is HOST at stage 0 with detail = the kind.  PGPU_EINVAL (with a
+ * message) also for bad parameters.  An empty plan is PGPU_OK.  A rerun gives the same bytes. */
+int pgpu_pairing_plan_run_factorization_lists(pgpu_ctx* ctx, pgpu_pairing_plan* plan, const pgpu_flist_params* params);
+/* factorizations and exons of the last run_factorization_lists (either pointer may be null) */
+int pgpu_pairing_plan_factorization_list_counts(const pgpu_pairing_plan* plan, uint64_t* n_facts, uint64_t* n_exons);
+/* out: n_pat results; PGPU_ENOSPC when facts_cap or exons_cap is smaller than the counts */
+int pgpu_pairing_plan_fetch_factorization_lists(pgpu_ctx* ctx, pgpu_pairing_plan* plan, pgpu_flist_result* out,
+                                                pgpu_flist_fact* facts, size_t facts_cap, pgpu_factor* exons, uint8_t* steps,
+                                                size_t exons_cap);
+/* HIP-event times of the last run_factorization_lists: k = 0 the whole call, 1 clean_kernel, 2 flist_select_kernel,
+ * 3 gaps_kernel, 4 chain_kernel; 0 without timing */
+double pgpu_pairing_plan_factorization_lists_ms(const pgpu_pairing_plan* plan, int k);
+
+/* ------------------------------------------------------------------------------------------ */
 /* final factorizations -- the factorization stage above, then pgpu_index_tail_chains and      */
 /* pgpu_index_small_chains on what it left, in ONE call, nothing leaving HBM in between: for an */
 /* EST with exactly one candidate this ends with the factorization as refine_EST_factorizations */

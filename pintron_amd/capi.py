@@ -157,6 +157,28 @@ class FactResult(C.Structure):     # pgpu_fact_result
 FactQuery = GapsQuery              # pgpu_fact_query: n_exons == 0 is "no candidate"
 
 
+class FlistParams(C.Structure):    # pgpu_flist_params
+    _fields_ = [("complexity_threshold", C.c_double), ("suffpref_length_on_est", C.c_int32),
+                ("suffpref_length_for_intron", C.c_int32), ("suffpref_length_on_gen", C.c_int32), ("min_intron_length", C.c_int32),
+                ("max_coverage_diff", C.c_double), ("max_site_difference", C.c_int32), ("max_gaplength_diff", C.c_int32),
+                ("max_number_of_factorizations", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class FlistQuery(C.Structure):     # pgpu_flist_query
+    _fields_ = [("est_off", C.c_uint64), ("est_len", C.c_uint32), ("first_candidate", C.c_uint32), ("n_candidates", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class FlistResult(C.Structure):    # pgpu_flist_result
+    _fields_ = [("outcome", C.c_uint8), ("stage", C.c_uint8), ("detail", C.c_uint16), ("first_fact", C.c_uint32),
+                ("n_facts", C.c_uint16), ("n_cleaned", C.c_uint16), ("n_listed", C.c_uint16), ("n_filtered", C.c_uint16)]
+
+
+class FlistFact(C.Structure):      # pgpu_flist_fact
+    _fields_ = [("first_exon", C.c_uint32), ("n_exons", C.c_uint16), ("n_merged", C.c_uint16), ("candidate", C.c_uint32),
+                ("total_edit", C.c_uint16), ("flags", C.c_uint16)]
+
+
 class FinalResult(C.Structure):    # pgpu_final_result
     _fields_ = [("outcome", C.c_uint8), ("stage", C.c_uint8), ("detail", C.c_uint16), ("first_exon", C.c_uint32),
                 ("n_exons", C.c_uint16), ("n_merged", C.c_uint16), ("total_edit", C.c_uint32), ("tail_added", C.c_uint32),
@@ -240,6 +262,15 @@ FACT_PARAMS_DTYPE = [("complexity_threshold", "<f8"), ("suffpref_length_on_est",
 FACT_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("first_exon", "<u4"), ("n_exons", "<u2"),
                      ("n_merged", "<u2"), ("total_edit", "<u4")]
 FACT_QUERY_DTYPE = GAPS_QUERY_DTYPE
+FLIST_MAX_CANDIDATES, FLIST_CAP_CANDIDATES = 64, 4
+FLIST_DROPPED_FIRST, FLIST_HEAD_WIDENED, FLIST_TAIL_WIDENED = 1, 2, 4
+FLIST_PARAMS_DTYPE = FACT_PARAMS_DTYPE + [("max_coverage_diff", "<f8"), ("max_site_difference", "<i4"), ("max_gaplength_diff", "<i4"),
+                                          ("max_number_of_factorizations", "<i4"), ("reserved", "<u4")]
+FLIST_QUERY_DTYPE = [("est_off", "<u8"), ("est_len", "<u4"), ("first_candidate", "<u4"), ("n_candidates", "<u4"), ("reserved", "<u4")]
+FLIST_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("first_fact", "<u4"), ("n_facts", "<u2"),
+                      ("n_cleaned", "<u2"), ("n_listed", "<u2"), ("n_filtered", "<u2")]
+FLIST_FACT_DTYPE = [("first_exon", "<u4"), ("n_exons", "<u2"), ("n_merged", "<u2"), ("candidate", "<u4"), ("total_edit", "<u2"),
+                    ("flags", "<u2")]
 FINAL_RESULT_DTYPE = [("outcome", "u1"), ("stage", "u1"), ("detail", "<u2"), ("first_exon", "<u4"), ("n_exons", "<u2"),
                       ("n_merged", "<u2"), ("total_edit", "<u4"), ("tail_added", "<u4"), ("polyA", "u1"), ("polyadenil", "u1"),
                       ("recovered", "u1"), ("refused", "u1"), ("n_removed", "<u2"), ("n_added", "<u2"), ("n_cleaned", "<u2"),
@@ -276,6 +307,7 @@ assert C.sizeof(SmallParams) == 8 and C.sizeof(SmallResult) == 24
 assert C.sizeof(CandParams) == 8 and C.sizeof(CandResult) == 16
 assert C.sizeof(FactParams) == 24 and C.sizeof(FactResult) == 16
 assert C.sizeof(FinalResult) == 32 and C.sizeof(FinalQuery) == 32
+assert C.sizeof(FlistParams) == 48 and C.sizeof(FlistQuery) == 24 and C.sizeof(FlistResult) == 16 and C.sizeof(FlistFact) == 16
 assert C.sizeof(UnitQuery) == 16 and C.sizeof(UnitParams) == 8 and C.sizeof(UnitResult) == 24
 assert C.sizeof(TextResult) == 32
 assert C.sizeof(SideResult) == 40
@@ -305,6 +337,9 @@ EXPORTS = [
     "pgpu_pairing_plan_candidate_lists_ms", "pgpu_index_candidate_lists", "pgpu_index_candidate_lists_kernel_ms",
     "pgpu_pairing_plan_run_factorizations", "pgpu_pairing_plan_factorization_exons", "pgpu_pairing_plan_fetch_factorizations",
     "pgpu_pairing_plan_factorizations_ms", "pgpu_index_factorizations", "pgpu_index_factorizations_kernel_ms",
+    "pgpu_index_factorization_lists", "pgpu_index_factorization_lists_kernel_ms", "pgpu_pairing_plan_run_factorization_lists",
+    "pgpu_pairing_plan_factorization_list_counts", "pgpu_pairing_plan_fetch_factorization_lists",
+    "pgpu_pairing_plan_factorization_lists_ms",
     "pgpu_pairing_plan_create_with_originals", "pgpu_pairing_plan_run_final_factorizations", "pgpu_pairing_plan_final_exons",
     "pgpu_pairing_plan_fetch_final_factorizations", "pgpu_pairing_plan_final_ms", "pgpu_index_final_factorizations",
     "pgpu_index_final_factorizations_kernel_ms",
@@ -431,6 +466,18 @@ def lib():
                                                 C.POINTER(C.c_uint8), sz, C.POINTER(sz)]
         L.pgpu_index_factorizations_kernel_ms.argtypes = []
         L.pgpu_index_factorizations_kernel_ms.restype = C.c_double
+        L.pgpu_index_factorization_lists.argtypes = [vp, vp, C.c_char_p, sz, C.POINTER(EnumCandidate), sz, C.POINTER(Factor), sz,
+                                                     C.POINTER(FlistQuery), sz, C.POINTER(FlistParams), C.POINTER(FlistResult),
+                                                     C.POINTER(FlistFact), sz, C.POINTER(Factor), C.POINTER(C.c_uint8), sz,
+                                                     C.POINTER(sz), C.POINTER(sz)]
+        L.pgpu_index_factorization_lists_kernel_ms.argtypes = []
+        L.pgpu_index_factorization_lists_kernel_ms.restype = C.c_double
+        L.pgpu_pairing_plan_run_factorization_lists.argtypes = [vp, vp, C.POINTER(FlistParams)]
+        L.pgpu_pairing_plan_factorization_list_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+        L.pgpu_pairing_plan_fetch_factorization_lists.argtypes = [vp, vp, C.POINTER(FlistResult), C.POINTER(FlistFact), sz,
+                                                                  C.POINTER(Factor), C.POINTER(C.c_uint8), sz]
+        L.pgpu_pairing_plan_factorization_lists_ms.argtypes = [vp, C.c_int]
+        L.pgpu_pairing_plan_factorization_lists_ms.restype = C.c_double
         L.pgpu_pairing_plan_create_with_originals.argtypes = [vp, vp, C.c_char_p, C.POINTER(u64), sz, C.c_int,
                                                               C.POINTER(C.c_uint32), C.POINTER(u64), C.c_char_p, sz, C.POINTER(vp)]
         L.pgpu_pairing_plan_run_final_factorizations.argtypes = [vp, vp, C.POINTER(SmallParams)]
@@ -890,6 +937,37 @@ class Index:
     def factorizations_kernel_ms(self):
         return self.ctx.L.pgpu_index_factorizations_kernel_ms()
 
+    def factorization_lists_raw(self, ests: bytes, cands, exons, queries, n: int, params, facts_cap: int, exons_cap: int):
+        """One pgpu_index_factorization_lists call as it is: `cands` a numpy array of ENUM_CANDIDATE_DTYPE, `exons` one of
+        FACTOR_DTYPE, `queries` one of FLIST_QUERY_DTYPE, `params` a FlistParams.  Returns (rc, results as a numpy array of
+        FLIST_RESULT_DTYPE, facts (facts_cap entries of FLIST_FACT_DTYPE), exons and step bytes (exons_cap entries each),
+        n_facts, n_exons)."""
+        import numpy as np
+        res = np.zeros(n, dtype=np.dtype(FLIST_RESULT_DTYPE))
+        facts = np.zeros(facts_cap, dtype=np.dtype(FLIST_FACT_DTYPE))
+        out_exons = np.zeros(exons_cap, dtype=np.dtype(FACTOR_DTYPE))
+        out_steps = np.zeros(exons_cap, dtype=np.uint8)
+        nf, ne = C.c_size_t(0), C.c_size_t(0)
+        rc = self.ctx.L.pgpu_index_factorization_lists(
+            self.ctx.h, self.h, ests, len(ests), cands.ctypes.data_as(C.POINTER(EnumCandidate)), len(cands),
+            exons.ctypes.data_as(C.POINTER(Factor)), len(exons), queries.ctypes.data_as(C.POINTER(FlistQuery)), n, C.byref(params),
+            res.ctypes.data_as(C.POINTER(FlistResult)), facts.ctypes.data_as(C.POINTER(FlistFact)), facts_cap,
+            out_exons.ctypes.data_as(C.POINTER(Factor)), out_steps.ctypes.data_as(C.POINTER(C.c_uint8)), exons_cap,
+            C.byref(nf), C.byref(ne))
+        return rc, res, facts, out_exons, out_steps, nf.value, ne.value
+
+    def factorization_lists(self, ests: bytes, cands, exons, queries, params=None):
+        """Every EST `queries` names, from its candidates to its list of factorizations, in one call: (results as a numpy
+        array of FLIST_RESULT_DTYPE, facts as one of FLIST_FACT_DTYPE, the final exons, compact, and their step bytes)."""
+        prm = params if params is not None else flist_params()
+        rc, res, facts, out_exons, out_steps, nf, ne = self.factorization_lists_raw(ests, cands, exons, queries, len(queries), prm,
+                                                                                    len(cands), len(exons))
+        self.ctx.check(rc)
+        return res, facts[:nf], out_exons[:ne], out_steps[:ne]
+
+    def factorization_lists_kernel_ms(self):
+        return self.ctx.L.pgpu_index_factorization_lists_kernel_ms()
+
     def final_factorizations_raw(self, ests: bytes, exons, queries, n: int, params, small_params, cap: int, wide: bool = False):
         """One pgpu_index_final_factorizations call as it is (wide: pgpu_index_final_factorizations_wide): `exons` a numpy array of FACTOR_DTYPE, `queries` one of
         FINAL_QUERY_DTYPE, `params` a FactParams, `small_params` a SmallParams or None.  Returns (rc, results as a numpy array
@@ -926,6 +1004,43 @@ class Index:
         if self.h:
             self.ctx.L.pgpu_index_destroy(self.ctx.h, self.h)
             self.h = C.c_void_p()
+
+
+def flist_params(complexity_threshold=20.0, suffpref_length_on_est=30, suffpref_length_for_intron=70, suffpref_length_on_gen=30,
+                 min_intron_length=40, max_coverage_diff=0.05, max_site_difference=50, max_gaplength_diff=20,
+                 max_number_of_factorizations=0, reserved=0):
+    """pgpu_flist_params; the defaults are the reference's configuration (src/options.ggo)"""
+    return FlistParams(complexity_threshold, suffpref_length_on_est, suffpref_length_for_intron, suffpref_length_on_gen,
+                       min_intron_length, max_coverage_diff, max_site_difference, max_gaplength_diff, max_number_of_factorizations,
+                       reserved)
+
+
+def flist_handoffs_probe(ctx, idx, ests, cands, exons, queries, params, gaps_results, gaps_exons, gaps_steps):
+    """pgpu_flist_handoffs_probe (pintron_amd/csrc/pgpu_flists.hip; no part of the C-ABI's header):
+    pgpu_index_factorization_lists with gaps_kernel's three outputs given -- `gaps_results` a numpy array of GAPS_RESULT_DTYPE
+    with one entry per candidate, `gaps_exons` (FACTOR_DTYPE) and `gaps_steps` (uint8) with len(exons) + len(cands) entries
+    each -- instead of computed.  Returns (rc, results, facts, exons, steps)."""
+    import numpy as np
+    assert len(gaps_results) == len(cands) and len(gaps_exons) == len(gaps_steps) == len(exons) + len(cands)
+    sz = C.c_size_t
+    f = ctx.L.pgpu_flist_handoffs_probe
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, sz, C.POINTER(EnumCandidate), sz, C.POINTER(Factor), sz, C.POINTER(FlistQuery), sz,
+                  C.POINTER(FlistParams), C.POINTER(FlistResult), C.POINTER(FlistFact), sz, C.POINTER(Factor), C.POINTER(C.c_uint8), sz,
+                  C.POINTER(sz), C.POINTER(sz), C.POINTER(GapsResult), C.POINTER(Factor), C.POINTER(C.c_uint8)]
+    n = len(queries)
+    res = np.zeros(n, dtype=np.dtype(FLIST_RESULT_DTYPE))
+    facts = np.zeros(len(cands), dtype=np.dtype(FLIST_FACT_DTYPE))
+    out_exons = np.zeros(len(exons), dtype=np.dtype(FACTOR_DTYPE))
+    out_steps = np.zeros(len(exons), dtype=np.uint8)
+    nf, ne = sz(0), sz(0)
+    rc = f(ctx.h, idx.h, ests, len(ests), cands.ctypes.data_as(C.POINTER(EnumCandidate)), len(cands),
+           exons.ctypes.data_as(C.POINTER(Factor)), len(exons), queries.ctypes.data_as(C.POINTER(FlistQuery)), n, C.byref(params),
+           res.ctypes.data_as(C.POINTER(FlistResult)), facts.ctypes.data_as(C.POINTER(FlistFact)), len(facts),
+           out_exons.ctypes.data_as(C.POINTER(Factor)), out_steps.ctypes.data_as(C.POINTER(C.c_uint8)), len(out_exons),
+           C.byref(nf), C.byref(ne), gaps_results.ctypes.data_as(C.POINTER(GapsResult)), gaps_exons.ctypes.data_as(C.POINTER(Factor)),
+           gaps_steps.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return rc, res, facts[:nf.value], out_exons[:ne.value], out_steps[:ne.value]
 
 
 def final_handoffs_probe(ctx, tlen, ests_len, q, fres, fex, tres, tex, tst, sres, sex, sst):
@@ -1246,6 +1361,42 @@ class PairingPlan:
     def factorizations_ms(self, k=0):
         """HIP-event time of the last run_factorizations: k = 0 the whole call, 1 clean, 2 gaps, 3 refine"""
         return self.ctx.L.pgpu_pairing_plan_factorizations_ms(self.h, k)
+
+    def run_factorization_lists(self, params=None):
+        """the candidate lists of the last run_candidate_lists to lists of factorizations, where they lie"""
+        prm = params if params is not None else flist_params()
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_run_factorization_lists(self.ctx.h, self.h, C.byref(prm)))
+        return self
+
+    def factorization_list_counts(self):
+        nf, ne = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.check(self.ctx.L.pgpu_pairing_plan_factorization_list_counts(self.h, C.byref(nf), C.byref(ne)))
+        return nf.value, ne.value
+
+    def fetch_factorization_lists_raw(self, facts_cap=None, exons_cap=None):
+        import numpy as np
+        nf, ne = self.factorization_list_counts()
+        facts_cap = nf if facts_cap is None else facts_cap
+        exons_cap = ne if exons_cap is None else exons_cap
+        res = np.zeros(self.n_pat, dtype=np.dtype(FLIST_RESULT_DTYPE))
+        facts = np.zeros(facts_cap, dtype=np.dtype(FLIST_FACT_DTYPE))
+        exons = np.zeros(exons_cap, dtype=np.dtype(FACTOR_DTYPE))
+        steps = np.zeros(exons_cap, dtype=np.uint8)
+        rc = self.ctx.L.pgpu_pairing_plan_fetch_factorization_lists(
+            self.ctx.h, self.h, res.ctypes.data_as(C.POINTER(FlistResult)), facts.ctypes.data_as(C.POINTER(FlistFact)), facts_cap,
+            exons.ctypes.data_as(C.POINTER(Factor)), steps.ctypes.data_as(C.POINTER(C.c_uint8)), exons_cap)
+        return rc, res, facts, exons, steps
+
+    def fetch_factorization_lists(self):
+        """(results as a numpy array of FLIST_RESULT_DTYPE, one per pattern; facts as one of FLIST_FACT_DTYPE; the final exons,
+        compact; their step bytes)"""
+        rc, res, facts, exons, steps = self.fetch_factorization_lists_raw()
+        self.ctx.check(rc)
+        return res, facts, exons, steps
+
+    def factorization_lists_ms(self, k=0):
+        """HIP-event time of the last run_factorization_lists: k = 0 the whole call, 1 clean, 2 select, 3 gaps, 4 refine"""
+        return self.ctx.L.pgpu_pairing_plan_factorization_lists_ms(self.h, k)
 
     def run_final_factorizations_raw(self, min_intron_length=40, reserved=0, no_params=False, wide=False):
         prm = SmallParams(min_intron_length, reserved)

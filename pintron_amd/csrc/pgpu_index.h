@@ -96,6 +96,7 @@ enum PlanSlot : int {
   SLOT_TEXTS, SLOT_TEXT_BLOBS,
   SLOT_SIDES, SLOT_SIDE_BLOBS,
   SLOT_ENUM, SLOT_ENUM_OUT,
+  SLOT_FLIST, SLOT_FLIST_WS,
   PLAN_SLOTS
 };
 bool pgpu_ctx_pool_acquire(pgpu_ctx* ctx, int pool);
@@ -165,6 +166,31 @@ inline int pgpu_clean_undersized(pgpu_ctx* ctx, const char* what) {
   snprintf(msg, sizeof msg, "%s: the workspace of a wave was sized too small for an end-exon alignment", what);
   return pgpu_ctx_fail(ctx, PGPU_EDEVICE, msg);
 }
+// pgpu_flists.hip: the candidate lists of n ESTs (`cands`: n_cands entries, `cand_exons`: n_exons_total, both in HBM) through
+// clean, the selection (add_if_not_exists, FILTER 1, FILTER 3), gaps and refine, all on the device.  `block` holds
+// flist_layout(n, n_cands, n_exons_total, pgpu_scan_tmp_bytes(n + 1)).total bytes (pgpu_flists.h), where the outcomes (res), the
+// factorizations (facts), the compact exons and their step bytes are found afterwards.  The ESTs are either queries (q) or a
+// plan's pattern offsets and enumeration results (pat_off, enum_res; q null); cand_exons may be the block's ex_in itself.
+// ws_alloc, the two waits and `undersized` as in pgpu_fact_job.
+struct pgpu_flist_job {
+  const uint8_t* T; uint32_t tlen;
+  const uint8_t* ests;
+  const pgpu_flist_query* q;
+  const unsigned long long* pat_off; const pgpu_enum_result* enum_res;
+  const pgpu_enum_candidate* cands; const pgpu_factor* cand_exons;
+  uint32_t n, n_cands, n_exons_total;
+  uint8_t* block;
+  void* (*ws_alloc)(void* user, size_t bytes); void* ws_user;
+  hipEvent_t ev[10];           // null without timing: 0-1 the whole drive, 2-3 clean, 4-5 select, 6-7 gaps, 8-9 chain
+  unsigned long long total_facts, total_exons; uint32_t undersized;
+  // Null in every call of the library.  pgpu_flist_handoffs_probe sets it: host arrays in the layout of the block's gr
+  // (n_cands), ex_gaps and gsteps (n_exons_total + n_cands each) that are copied in where gaps_kernel would have written
+  // them, and the kernel is not launched -- the hand-off kernels behind it then run over results no input brings through
+  // gaps_kernel (two kept exons out of order)
+  struct Given { const pgpu_gaps_result* results; const pgpu_factor* exons; const uint8_t* steps; };
+  const Given* given_gaps;
+};
+hipError_t pgpu_flist_drive(pgpu_ctx* ctx, pgpu_flist_job& job, const pgpu_flist_params& prm);
 // pgpu_final.hip: the answer of pgpu_fact_drive, where it lies (`fact_block`, the block of a job of the same n and
 // n_exons_total, read only), through the tail and the small stage.  The ESTs are either the queries of the index form (fq) or
 // a plan's pattern offsets and its table of original offsets (pat_off, orig_off; fq null); `ests_len` bytes lie behind

@@ -22,6 +22,7 @@
 #include "pgpu_stage_drive.h"
 #include "pgpu_enum.h"
 #include "pgpu_fact.h"
+#include "pgpu_flists.h"
 #include "pgpu_final.h"
 #include "pgpu_unit.h"
 #include "pgpu_side.h"
@@ -376,12 +377,15 @@ void pair_emit_kernel(const unsigned long long* __restrict__ pat_off,
 // RECORDS made with the same min_factor_len and never changes `stage`; its results live in pool slots of their own
 // (SLOT_ENUM, SLOT_ENUM_OUT) under a flag of their own (lists_valid), which run and run_meg clear and which the run of
 // another resident plan overrules (overwritten); run_candidates and the rungs above it neither need nor disturb them.
+// The factorization lists (run_factorization_lists, pgpu_flists.hip) are a second branch, built the same way: the run asks
+// for valid candidate lists and reads them where they lie; its results live in SLOT_FLIST (the workspace in SLOT_FLIST_WS)
+// under flists_valid, which run, run_meg and run_candidate_lists clear; it needs and disturbs no rung.
 enum Stage : int { NOTHING, PAIRINGS, RECORDS, CANDIDATES, FACTORIZATIONS, FINALS, UNITS, TEXTS, SIDES };
 
 // the plan's events (made only when the context times its calls): seven around the six pairing stages, a pair each for
 // the MEG and the candidate stage, the eight of pgpu_fact_job, the six of pgpu_final_job, the pair of pgpu_unit_job, the
-// three of pgpu_text_job, the three of pgpu_side_job, the pair of the candidate lists
-enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, EV_TEXTS = 27, EV_SIDES = 30, EV_LISTS = 33, N_EVENTS = 35 };
+// three of pgpu_text_job, the three of pgpu_side_job, the pair of the candidate lists, the ten of pgpu_flist_job
+enum { EV_PAIRS = 0, EV_MEG = 7, EV_CAND = 9, EV_FACT = 11, EV_FINAL = 19, EV_UNITS = 25, EV_TEXTS = 27, EV_SIDES = 30, EV_LISTS = 33, EV_FLISTS = 35, N_EVENTS = 45 };
 
 struct pgpu_pairing_plan {
   pgpu_ctx* owner = nullptr;
@@ -468,6 +472,13 @@ struct pgpu_pairing_plan {
   unsigned long long lists_cands = 0, lists_exons = 0;
   bool lists_valid = false;
   float lists_ms = 0.f;
+  // factorization lists (pgpu_flists.hip) over those candidate lists, beside the ladder too: the driver's block
+  // (flist_layout of pgpu_flists.h, for the counts the lists had at the run) and the workspace of clean and refine
+  uint8_t *d_flist = nullptr, *d_flist_ws = nullptr;
+  size_t flist_cap = 0, flist_ws_cap = 0;
+  unsigned long long flist_cands = 0, flist_cand_exons = 0, flist_facts = 0, flist_exons = 0;
+  bool flists_valid = false;
+  float flist_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 };
 
 static void lower(pgpu_pairing_plan* p, Stage s) { if (p->stage > s) p->stage = s; }
@@ -575,6 +586,7 @@ static void pairing_plan_free(pgpu_pairing_plan* p) {
     hipFree(p->d_cand_res); hipFree(p->d_cand_cnt); hipFree(p->d_cand_first); hipFree(p->d_cand_exons);
     hipFree(p->d_fact); hipFree(p->d_fact_ws); hipFree(p->d_final); hipFree(p->d_unit); hipFree(p->d_text); hipFree(p->d_text_blobs);
     hipFree(p->d_side); hipFree(p->d_side_blobs); hipFree(p->d_lists); hipFree(p->d_lists_out);
+    hipFree(p->d_flist); hipFree(p->d_flist_ws);
     if (p->d_orig_off != p->d_pat_off) hipFree(p->d_orig_off);
   }
   for (auto& e : p->ev) if (e) hipEventDestroy(e);
@@ -671,7 +683,7 @@ extern "C" int pgpu_pairing_plan_run(pgpu_ctx* ctx, pgpu_pairing_plan* p, const 
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   p->n_cand = p->n_out = 0;
   lower(p, NOTHING);
-  p->lists_valid = false;
+  p->lists_valid = p->flists_valid = false;
   p->last_L = params->min_factor_len;
   if (p->n_pat == 0) return reached(p, PAIRINGS);
   if (p->resident) {
@@ -737,7 +749,7 @@ extern "C" int pgpu_pairing_plan_run_meg(pgpu_ctx* ctx, pgpu_pairing_plan* p, co
   if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
   p->meg_total = 0; p->meg_ms = 0.f;
   lower(p, PAIRINGS);
-  p->lists_valid = false;
+  p->lists_valid = p->flists_valid = false;
   if (p->n_pat == 0) return reached(p, RECORDS);
   if (p->stage < PAIRINGS || p->last_L != prm->min_factor_len)
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_meg needs the pairings of pgpu_pairing_plan_run with the same min_factor_len");
@@ -842,7 +854,7 @@ extern "C" int pgpu_pairing_plan_fetch_candidates(pgpu_ctx* ctx, pgpu_pairing_pl
 extern "C" int pgpu_pairing_plan_run_candidate_lists(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_cand_params* prm) {
   if (!ctx || !p || !prm) return PGPU_EINVAL;
   p->lists_cands = p->lists_exons = 0; p->lists_ms = 0.f;
-  p->lists_valid = false;                              // its own results are gone, even when the call is then refused
+  p->lists_valid = p->flists_valid = false;            // its own results are gone, even when the call is then refused
   if (prm->min_factor_len == 0 || prm->min_factor_len > (1u << 24))
     return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad candidate parameters (min_factor_len 0 or above 2^24)");
   if (p->n_pat == 0) { p->lists_valid = true; return PGPU_OK; }
@@ -910,6 +922,86 @@ extern "C" int pgpu_pairing_plan_fetch_candidate_lists(pgpu_ctx* ctx, pgpu_pairi
     PLAN_TRY(hipMemcpyAsync(cands, p->d_lists_out + O.cands, (size_t)p->lists_cands * sizeof(pgpu_enum_candidate), hipMemcpyDeviceToHost, st));
   if (p->lists_exons)
     PLAN_TRY(hipMemcpyAsync(exons, p->d_lists_out + O.exons, (size_t)p->lists_exons * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
+  PLAN_TRY(pgpu_ctx_wait(ctx));
+  return PGPU_OK;
+}
+
+// ---- the candidate lists of the last run_candidate_lists to lists of factorizations, where they lie (pgpu_flists.hip);
+// beside the ladder ----
+extern "C" int pgpu_pairing_plan_run_factorization_lists(pgpu_ctx* ctx, pgpu_pairing_plan* p, const pgpu_flist_params* prm) {
+  if (!ctx || !p || !prm) return PGPU_EINVAL;
+  p->flist_facts = p->flist_exons = 0;
+  for (auto& m : p->flist_ms) m = 0.f;
+  p->flists_valid = false;                             // its own results are gone, even when the call is then refused
+  if (!flist_params_ok(*prm))
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "bad factorization-list parameters (a setting outside its range, or reserved != 0)");
+  if (p->n_pat == 0) { p->flists_valid = true; return PGPU_OK; }
+  if (!p->lists_valid)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "run_factorization_lists needs the candidate lists of pgpu_pairing_plan_run_candidate_lists");
+  if (const int rc = still_owns(ctx, p, "candidate lists")) return rc;
+  if (p->n_pat > 0x7fffffffull || p->lists_cands > 0x7fffffffull || p->lists_exons > 0x7fffffffull)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "more than 2^31 - 1 patterns, candidates or candidate exons in one plan");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  if (p->resident) p->d_flist_ws = nullptr;                                    // taken anew, as the block: the pool may have moved
+  const ProfRange range("factorization lists");
+  const FlistLayout L = flist_layout(p->n_pat, (size_t)p->lists_cands, (size_t)p->lists_exons, pgpu_scan_tmp_bytes(p->n_pat + 1));
+  PLAN_NEED(p->d_flist = stage_block(p, p->d_flist, &p->flist_cap, L.total, SLOT_FLIST));
+  PLAN_TRY(plan_events(p, EV_FLISTS, 10));
+  const EnumLayout E = enum_layout(0, p->n_pat, 0);
+  const EnumOutLayout O = enum_out_layout((size_t)p->lists_cands, (size_t)p->lists_exons);
+  pgpu_flist_job job;
+  job.T = p->ix.T; job.tlen = p->ix.n; job.ests = p->d_pats;
+  job.q = nullptr; job.pat_off = p->d_pat_off; job.enum_res = (const pgpu_enum_result*)(p->d_lists + E.res);
+  job.cands = (const pgpu_enum_candidate*)(p->d_lists_out + O.cands); job.cand_exons = (const pgpu_factor*)(p->d_lists_out + O.exons);
+  job.n = (uint32_t)p->n_pat; job.n_cands = (uint32_t)p->lists_cands; job.n_exons_total = (uint32_t)p->lists_exons;
+  job.block = p->d_flist;
+  job.ws_alloc = [](void* user, size_t bytes) -> void* {
+    pgpu_pairing_plan* q = (pgpu_pairing_plan*)user;
+    return q->d_flist_ws = plan_grow(q, q->d_flist_ws, &q->flist_ws_cap, bytes, 0, SLOT_FLIST_WS);
+  };
+  job.ws_user = p;
+  for (int k = 0; k < 10; ++k) job.ev[k] = p->ev[EV_FLISTS + k];
+  job.given_gaps = nullptr;
+  PLAN_TRY(pgpu_flist_drive(ctx, job, *prm));
+  if (job.undersized) return pgpu_clean_undersized(ctx, "factorization lists");
+  p->flist_cands = p->lists_cands; p->flist_cand_exons = p->lists_exons;
+  p->flist_facts = job.total_facts; p->flist_exons = job.total_exons;
+  elapsed_pairs(p, EV_FLISTS, 5, p->flist_ms);
+  p->flists_valid = true;
+  return PGPU_OK;
+}
+
+extern "C" int pgpu_pairing_plan_factorization_list_counts(const pgpu_pairing_plan* p, uint64_t* n_facts, uint64_t* n_exons) {
+  if (!p) return PGPU_EINVAL;
+  if (n_facts) *n_facts = p->flist_facts;
+  if (n_exons) *n_exons = p->flist_exons;
+  return PGPU_OK;
+}
+extern "C" double pgpu_pairing_plan_factorization_lists_ms(const pgpu_pairing_plan* p, int k) {
+  return (p && k >= 0 && k < 5) ? p->flist_ms[k] : 0.0;
+}
+
+extern "C" int pgpu_pairing_plan_fetch_factorization_lists(pgpu_ctx* ctx, pgpu_pairing_plan* p, pgpu_flist_result* out,
+                                                           pgpu_flist_fact* facts, size_t facts_cap, pgpu_factor* exons,
+                                                           uint8_t* steps, size_t exons_cap) {
+  if (!ctx || !p || (p->n_pat && !out) || (facts_cap && !facts) || (exons_cap && (!exons || !steps))) return PGPU_EINVAL;
+  if (const int rc = still_owns(ctx, p, "factorization lists")) return rc;
+  if (!p->flists_valid)
+    return pgpu_ctx_fail(ctx, PGPU_EINVAL, "fetch_factorization_lists needs pgpu_pairing_plan_run_factorization_lists behind the last "
+                                           "run, run_meg and run_candidate_lists");
+  if (facts_cap < p->flist_facts) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "factorization buffer too small");
+  if (exons_cap < p->flist_exons) return pgpu_ctx_fail(ctx, PGPU_ENOSPC, "exon buffer too small");
+  if (pgpu_ctx_bind(ctx) != PGPU_OK) return PGPU_EDEVICE;
+  hipStream_t st = pgpu_ctx_stream(ctx);
+  if (p->n_pat == 0) return PGPU_OK;
+  const FlistLayout L = flist_layout(p->n_pat, (size_t)p->flist_cands, (size_t)p->flist_cand_exons, pgpu_scan_tmp_bytes(p->n_pat + 1));
+  PLAN_TRY(hipMemcpyAsync(out, p->d_flist + L.res, p->n_pat * sizeof *out, hipMemcpyDeviceToHost, st));
+  if (p->flist_facts)
+    PLAN_TRY(hipMemcpyAsync(facts, p->d_flist + L.facts, (size_t)p->flist_facts * sizeof *facts, hipMemcpyDeviceToHost, st));
+  if (p->flist_exons) {
+    PLAN_TRY(hipMemcpyAsync(exons, p->d_flist + L.out_exons, (size_t)p->flist_exons * sizeof(pgpu_factor), hipMemcpyDeviceToHost, st));
+    PLAN_TRY(hipMemcpyAsync(steps, p->d_flist + L.out_steps, (size_t)p->flist_exons, hipMemcpyDeviceToHost, st));
+  }
   PLAN_TRY(pgpu_ctx_wait(ctx));
   return PGPU_OK;
 }

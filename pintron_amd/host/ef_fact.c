@@ -1414,3 +1414,98 @@ __attribute__((cold)) unsigned ef_chain_small(const char* EST, const char* ORIG,
 __attribute__((cold)) void ef_config_set_min_intron_length(ef_config* cfg, int min_intron_length) {
   cfg->min_intron_length = min_intron_length;
 }
+
+/* every setting the chain from the candidates to the refined lists reads, for a caller that holds the configuration as
+ * bytes (the tests of ef_chain_factorizations) */
+__attribute__((cold)) void ef_config_set_chain_settings(ef_config* cfg, double complexity_threshold, int suffpref_length_on_est,
+                                                        int suffpref_length_for_intron, int suffpref_length_on_gen,
+                                                        int min_intron_length, double max_coverage_diff, unsigned max_site_difference,
+                                                        int max_gapLength_diff, int max_number_of_factorizations) {
+  cfg->complexity_threshold = complexity_threshold; cfg->suffpref_length_on_est = suffpref_length_on_est;
+  cfg->suffpref_length_for_intron = suffpref_length_for_intron; cfg->suffpref_length_on_gen = suffpref_length_on_gen;
+  cfg->min_intron_length = min_intron_length; cfg->max_coverage_diff = max_coverage_diff;
+  cfg->max_site_difference = max_site_difference; cfg->max_gapLength_diff = max_gapLength_diff;
+  cfg->max_number_of_factorizations = max_number_of_factorizations;
+}
+
+/* filter_and_refine on the cleaned list, then the lists flattened: the end of the two routines below */
+static unsigned chain_lists_out(ef_list* flist, const ef_config* cfg, const char* EST, const char* GEN, ef_backend* be,
+                                ef_factor* out_exons, size_t exon_cap, unsigned* fact_first, size_t fact_cap, unsigned* n_facts,
+                                unsigned* n_exons) {
+  ef_seq est_info, gen_info;
+  memset(&est_info, 0, sizeof est_info); memset(&gen_info, 0, sizeof gen_info);
+  est_info.seq = est_info.original_seq = (char*)EST;
+  gen_info.seq = gen_info.original_seq = (char*)GEN;
+  flist = filter_and_refine(flist, (unsigned)strlen(EST), &est_info, &gen_info, cfg, be);
+  ef_iter fi = efl_begin(flist);
+  while (efi_has_next(&fi)) {
+    ef_list* f = (ef_list*)efi_next(&fi);
+    if (*n_facts < fact_cap) fact_first[*n_facts] = *n_exons;
+    ef_iter xi = efl_begin(f);
+    while (efi_has_next(&xi)) {
+      const ef_factor* x = (const ef_factor*)efi_next(&xi);
+      if (*n_exons < exon_cap) out_exons[*n_exons] = *x;
+      ++*n_exons;
+    }
+    ++*n_facts;
+    if (*n_facts <= fact_cap) fact_first[*n_facts] = *n_exons;
+  }
+  const unsigned outcome = efl_empty(flist) ? 1u : 2u;
+  efl_free(flist, ef_factorization_free);
+  return outcome;
+}
+
+/* One MEG record and one EST through everything ef_get_est_factorizations does for a graph that need not be one path, up to,
+ * not including, correct_tail: the root loop with subtree_embeddings (as ef_chain_candidates), clean_candidates per root on
+ * one growing list, then filter_and_refine -- the very routines of ef_get_est_factorizations, not copies -- what
+ * pgpu_index_factorization_lists computes on the device (include/pintron_gpu.h).  Returns 0 when the record is flagged, 1
+ * when no factorization is left, 2 with every factorization of the list: fact_first[f] .. fact_first[f + 1] delimits the
+ * exons of factorization f in out_exons; at most fact_cap factorizations (fact_first holds fact_cap + 1 entries) and exon_cap
+ * exons are written, *n_facts and *n_exons are the numbers there are.  No budget and no cap; a cyclic graph does not
+ * return; max_number_of_factorizations < 0 stays with the caller.  est-fact does not call this (cold). */
+__attribute__((cold)) unsigned ef_chain_factorizations(const void* rec, const ef_config* cfg, const char* EST, const char* GEN,
+                                                       ef_backend* be, ef_factor* out_exons, size_t exon_cap, unsigned* fact_first,
+                                                       size_t fact_cap, unsigned* n_facts, unsigned* n_exons) {
+  *n_facts = 0; *n_exons = 0;
+  if (((const uint32_t*)rec)[2] & 3u) return 0;
+  const unsigned est_len = (unsigned)strlen(EST);
+  ef_meg* V = ef_meg_from_record(rec, 0);
+  ef_work wk = { 0, ~0ull };
+  ef_list* flist = efl_new();
+  EF_MEG_FOR_POS(V, i, 0, V->n_act) {
+    ef_iter it = efl_begin(V->v[i]);
+    while (efi_has_next(&it)) {
+      ef_pairing* root = (ef_pairing*)efi_next(&it);
+      if (root->visited) continue;
+      ef_list* embs = subtree_embeddings(root, cfg, GEN, &wk);
+      flist = clean_candidates(factorizations_from_embeddings(embs, cfg), flist, est_len, GEN, EST, cfg, be);
+    }
+  }
+  EF_MEG_FOR_POS(V, i, 0, V->n_act) {
+    ef_iter it = efl_begin(V->v[i]);
+    while (efi_has_next(&it)) { ef_pairing* p = (ef_pairing*)efi_next(&it); if (p->emb_memo) { efl_free(p->emb_memo, embedding_free); p->emb_memo = NULL; } }
+  }
+  ef_meg_free(V);
+  return chain_lists_out(flist, cfg, EST, GEN, be, out_exons, exon_cap, fact_first, fact_cap, n_facts, n_exons);
+}
+
+/* The same from candidates a caller holds (cand_first[c] .. cand_first[c + 1] in exons), for the hand-made cases of the tests
+ * that no record gives: clean_candidates on them as one root's, then the same end.  Returns 1 or 2.  (cold) */
+__attribute__((cold)) unsigned ef_chain_factorizations_from(const ef_factor* exons, const unsigned* cand_first, unsigned n_cands,
+                                                            const ef_config* cfg, const char* EST, const char* GEN, ef_backend* be,
+                                                            ef_factor* out_exons, size_t exon_cap, unsigned* fact_first,
+                                                            size_t fact_cap, unsigned* n_facts, unsigned* n_exons) {
+  *n_facts = 0; *n_exons = 0;
+  ef_list* cands = efl_new();
+  for (unsigned c = 0; c < n_cands; ++c) {
+    ef_list* f = efl_new();
+    for (unsigned k = cand_first[c]; k < cand_first[c + 1]; ++k) {
+      ef_factor* x = (ef_factor*)malloc(sizeof(ef_factor));
+      *x = exons[k];
+      efl_push_back(f, x);
+    }
+    efl_push_back(cands, f);
+  }
+  ef_list* flist = clean_candidates(cands, efl_new(), (unsigned)strlen(EST), GEN, EST, cfg, be);
+  return chain_lists_out(flist, cfg, EST, GEN, be, out_exons, exon_cap, fact_first, fact_cap, n_facts, n_exons);
+}

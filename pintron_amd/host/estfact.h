@@ -440,6 +440,21 @@ unsigned ef_chain_tail(const char* EST, const char* ORIG, const char* GEN, struc
 unsigned ef_chain_small(const char* EST, const char* ORIG, const ef_seq* gen, const ef_config* cfg, struct ef_backend* be,
                         ef_factor* exons, unsigned n_exons, unsigned cap, unsigned* n_out);
 void ef_config_set_min_intron_length(ef_config* cfg, int min_intron_length);
+/* One MEG record and one EST through the enumeration, the cleaning steps per candidate with add_if_not_exists, the filters
+ * and the refinement loop: every factorization get_EST_factorizations holds before correct_tail.  0 the record is flagged, 1
+ * no factorization, 2 with the lists flattened (fact_first[f] .. fact_first[f + 1] in out_exons).  What
+ * pgpu_index_factorization_lists answers on the device; est-fact does not call it */
+unsigned ef_chain_factorizations(const void* rec, const ef_config* cfg, const char* EST, const char* GEN, struct ef_backend* be,
+                                 ef_factor* out_exons, size_t exon_cap, unsigned* fact_first, size_t fact_cap, unsigned* n_facts,
+                                 unsigned* n_exons);
+/* the same from candidates the caller holds (cand_first[c] .. cand_first[c + 1] in exons): 1 or 2 */
+unsigned ef_chain_factorizations_from(const ef_factor* exons, const unsigned* cand_first, unsigned n_cands, const ef_config* cfg,
+                                      const char* EST, const char* GEN, struct ef_backend* be, ef_factor* out_exons, size_t exon_cap,
+                                      unsigned* fact_first, size_t fact_cap, unsigned* n_facts, unsigned* n_exons);
+void ef_config_set_chain_settings(ef_config* cfg, double complexity_threshold, int suffpref_length_on_est,
+                                  int suffpref_length_for_intron, int suffpref_length_on_gen, int min_intron_length,
+                                  double max_coverage_diff, unsigned max_site_difference, int max_gapLength_diff,
+                                  int max_number_of_factorizations);
 /* a factorization = ef_list of ef_factor*; a list of factorizations = ef_list of ef_list* */
 
 typedef struct {
